@@ -16,9 +16,12 @@ own independent filters (weak scaling, no data-path collective); the final poses
 once over RCCL. configs[3] (N=256 × 4096 filters over 8 GPUs) is
 `bench.py --workload swarm_n256_fp64 --gpus 8` (512 filters per rank).
 
-Also reported: the Σ-pass roofline (HIP events on the library's stream), the CPU baseline (the
-literal dense restatement of slam.cpp through numpy's OpenBLAS dgemm on the host cores, rank 0 at
-N=1 only; the C oracle's literal and O(n²) legs beside it) and pose parity of the first timed
+A plain run sets up, warms up, times --steps messages and prints the result line; --dump-outputs
+DIR also writes what those messages computed (final poses, state and Σ) as DIR/<name>.npy. With
+--full it also reports: the Σ-pass roofline (HIP events on the library's stream) and its HBM
+traffic (rocprofv3 --pmc child runs), the same span fed host arrays, the fp64 leg, the CPU baseline
+(the literal dense restatement of slam.cpp through numpy's OpenBLAS dgemm on the host cores, rank 0
+at N=1 only; the C oracle's literal and O(n²) legs beside it) and pose parity of the first timed
 messages against the fp64 oracle.
 """
 from __future__ import annotations
@@ -87,7 +90,17 @@ def parse(argv=None):
                         "rosbag_surrogate: configs[4]'s shape, scans → detect → slam node")
     p.add_argument("--seed", type=int, default=20240317,
                    help="filter g (global index over ranks) uses seed + g (SURVEY.md §8d)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and parity legs")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also run everything beside the headline figure: "
+                        "the Σ-pass roofline and HBM-traffic counters, the host-input span, the "
+                        "fp64 leg, pose parity against the oracle and the CPU baselines (the "
+                        "options below choose among them); without it the run sets up, warms up, "
+                        "times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed steps left behind (final poses, state vector and Σ "
+                        "of a fixed sample of filters) as DIR/<name>.npy, float64")
+    p.add_argument("--no-cpu", action="store_true",
+                   help="with --full: skip the CPU baseline and parity legs")
     p.add_argument("--inputs", choices=["auto", "host", "hbm", "device"], default="auto",
                    help="hbm: the pyekf.synth marker arrays uploaded to HBM before the timed region "
                         "and planned on the GPU (ekf_replay_device); device: odometry, slip and the "
@@ -98,10 +111,32 @@ def parse(argv=None):
                         "workloads, host otherwise (association, the resident N = 50)")
     p.add_argument("--parity-messages", type=int, default=10)
     p.add_argument("--traffic", choices=["auto", "off"], default="auto",
-                   help="auto: measure the Σ pass's HBM bytes with two rocprofv3 --pmc child runs")
+                   help="with --full, auto: measure the Σ pass's HBM bytes with rocprofv3 --pmc "
+                        "child runs")
     p.add_argument("--no-fp64", action="store_true",
-                   help="skip the n1024_fp32 line's fp64 leg (configs[2] at slam.cpp's arithmetic)")
+                   help="with --full: skip the n1024_fp32 line's fp64 leg (configs[2] at slam.cpp's "
+                        "arithmetic)")
     return p.parse_args(argv)
+
+
+DUMP_SIGMA_BYTES = 48 << 20  # --dump-outputs: Σ of as many sampled filters as fit in this
+DUMP_SAMPLE_SEED = 20240317  # the sample of filters is fixed (independent of --seed)
+
+
+def dump_filters(F, n):
+    """--dump-outputs: the filters whose state and Σ are written, every one where they fit,
+    else a fixed seeded sample (sorted)."""
+    k = int(max(1, min(F, DUMP_SIGMA_BYTES // (n * n * 8))))
+    if k == F:
+        return np.arange(F)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(F, k, replace=False))
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float64."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _pmc_pass(args, counters):
@@ -121,7 +156,7 @@ def _pmc_pass(args, counters):
     d = tempfile.mkdtemp(prefix="ekf_pmc_", dir=os.environ.get("TMPDIR", "/tmp"))
     cmd = [exe, "--pmc", *counters, "-d", d, "-o", "pmc", "--output-format", "csv", "--",
            sys.executable, os.path.abspath(__file__), "--workload", args.workload,
-           "--steps", "8", "--warmup", "2", "--no-cpu", "--traffic", "off", "--no-fp64"]
+           "--steps", "8", "--warmup", "2", "--full", "--no-cpu", "--traffic", "off", "--no-fp64"]
     env = dict(os.environ, EKF_SERIAL="1")
     name = " ".join(counters)
     try:
@@ -199,13 +234,18 @@ def frontend_main(args):
     amin, ainc = np.zeros(S), np.full(S, inc)
     det = Detector(max_scans=S, max_beams=B)
     for _ in range(max(args.warmup, 1)):
-        cnt, _ = det.detect(ranges, amin, ainc)
+        cnt, mk = det.detect(ranges, amin, ainc)
     kern = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        det.detect(ranges, amin, ainc)
+        cnt, mk = det.detect(ranges, amin, ainc)
         kern.append(det.last_kernel_us())
     wall = time.perf_counter() - t0
+    if args.dump_outputs:  # the last step's markers, slots past a scan's count zeroed
+        keep = np.arange(mk.shape[1])[None, :] < np.clip(cnt, 0, mk.shape[1])[:, None]
+        write_outputs(args.dump_outputs, {
+            "marker_counts": cnt,
+            "markers": np.stack([np.where(keep, mk[k], 0.0) for k in ("x", "y", "r")], -1)})
     k_us = float(np.mean(kern))
     in_bytes = S * B * 4 + S * 16
     result = {
@@ -224,7 +264,7 @@ def frontend_main(args):
         "host_inclusive": {"scans_per_s": S * args.steps / wall,
                            "note": "lm_detect call: ranges H2D, kernel, markers D2H, sync"},
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import landmarks_numpy as L  # noqa: E402  (cpu_baseline leg only)
         n_cpu = 64
@@ -269,20 +309,24 @@ def rosbag_main(args):
                              rel, c.astype(np.int32), sc.truth, sc.track, sc.radius)
         # no trace: the drive's messages are planned on the host and run as one submission
         _, poses, _ = s.replay(scg, poses=trace)
-        s.filter_state(sigma=False)               # the drive's end: synchronises
-        return scg, poses
+        x_end = s.filter_state(sigma=False)[0]    # the drive's end: synchronises
+        return scg, poses, x_end
     for _ in range(max(args.warmup, 1)):
         gpu_run(False)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        scg, _ = gpu_run(False)
+        scg, _, x_end = gpu_run(False)
     dt = (time.perf_counter() - t0) / args.steps
-    # device time of the EKF kernels over one more (untimed) drive, HIP events per launch
-    s.profile(True)
-    gpu_run(False)
-    dev = {k: s.profile_read(k) for k in (4, 1, 2, 3, 0)}
-    s.profile(False)
-    scg, poses = gpu_run(True)  # the pose trace for parity, untimed
+    if args.dump_outputs:  # the last timed drive: its markers per scan and the state it ended in
+        write_outputs(args.dump_outputs, {"state": x_end, "marker_counts": scg.count,
+                                          "markers": scg.rel})
+    if args.full:
+        # device time of the EKF kernels over one more (untimed) drive, HIP events per launch
+        s.profile(True)
+        gpu_run(False)
+        dev = {k: s.profile_read(k) for k in (4, 1, 2, 3, 0)}
+        s.profile(False)
+        scg, poses, _ = gpu_run(True)  # the pose trace for parity, untimed
     det.close()
     s.close()
     corr = int(scg.count.sum())
@@ -300,14 +344,15 @@ def rosbag_main(args):
                    "step": "slam_reset + lm_detect batch + 426 slam_markers messages with "
                            "wheel ticks (one deferred submission) + state read-back",
                    "device_path": "resident" if s.path == pyekf.EKF_PATH_RESIDENT else "pipeline"},
-        "ekf_device_ms_per_step": sum(v[1] for v in dev.values()),
-        "ekf_device_launches_per_step": {
-            {4: "k_resident", 1: "k_chain", 2: "k_assoc", 3: "k_factors", 0: "k_sigma_pass"}[k]: v[0]
-            for k, v in dev.items() if v[0]},
-        "pose_rmse_vs_truth_m": float(np.sqrt(np.mean(np.sum((poses[:, 1:] - tr[:, 1:]) ** 2,
-                                                               1)))),
     }
-    if not args.no_cpu:
+    if args.full:
+        result["ekf_device_ms_per_step"] = sum(v[1] for v in dev.values())
+        result["ekf_device_launches_per_step"] = {
+            {4: "k_resident", 1: "k_chain", 2: "k_assoc", 3: "k_factors", 0: "k_sigma_pass"}[k]: v[0]
+            for k, v in dev.items() if v[0]}
+        result["pose_rmse_vs_truth_m"] = float(np.sqrt(np.mean(np.sum(
+            (poses[:, 1:] - tr[:, 1:]) ** 2, 1))))
+    if args.full and not args.no_cpu:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import landmarks_numpy as L  # noqa: E402  (cpu_baseline / parity legs only)
         orc = _oracle()
@@ -428,7 +473,7 @@ def run(args, rank, world, local, backend=None):
     resident = dt == "f64" and 3 + 2 * N <= 128 and os.environ.get("EKF_RESIDENT") != "0"
     if resident:
         traffic_err = "resident path: Σ crosses HBM once per launch (no Σ pass to count)"
-    if args.traffic == "auto" and world == 1 and not resident and backend is None:
+    if args.full and args.traffic == "auto" and world == 1 and not resident and backend is None:
         traffic, traffic_err = pmc_traffic(args)  # child runs, before this process uses the GPU
     import torch.distributed as dist
     be = backend if backend is not None else HipBackend(local)
@@ -581,49 +626,60 @@ def run(args, rank, world, local, backend=None):
         elapsed, total_corr, all_poses = reduce_ranks(elapsed, corrections, poses, be.device)
     else:
         total_corr, all_poses = float(corrections), poses
+    if args.dump_outputs and rank == 0:
+        # what the K timed messages left: every filter's pose (all ranks'), and the state vector
+        # and Σ of this rank's sampled filters, read before anything else runs on the handle
+        picked = dump_filters(F, 3 + 2 * N)
+        xs, Ss = zip(*(ekf.state(int(f))[:2] for f in picked))
+        write_outputs(args.dump_outputs, {"poses": all_poses, "sampled_filters": picked,
+                                          "state": np.stack(xs), "sigma": np.stack(Ss)})
+        del xs, Ss
 
-    # ---- roofline pass: same work, Σ-pass launches bracketed by HIP events ----
-    ps = slice(t0s + K, t0s + 2 * K)
-    ekf.profile(True)
-    msgs(ps.start, ps.stop)
-    n_sig, ms_sig = ekf.profile_read(0)
-    n_gain, ms_gain = ekf.profile_read(1)
-    n_fac, ms_fac = ekf.profile_read(3)
-    n_res, ms_res = ekf.profile_read(4)
-    n_asc, ms_asc = ekf.profile_read(2)
-    ekf.profile(False)
-    live = np.arange(act.shape[2]) < counts[ps][..., None]
-    res_corr = int(np.count_nonzero(live & (act[ps] != 2)))
     host_rate = None
-    if inputs == "hbm":  # the same path fed host arrays (ekf_replay): host planning and PCIe timed
-        hs = slice(t0s + 2 * K, t0s + 3 * K)
-        ekf.sync()  # (the planning state comes back from the device first: not this span's cost)
-        if world > 1:
-            dist.barrier()
-        be.sync()
-        t1 = time.perf_counter()
-        msgs(hs.start, hs.stop, host=True)
-        be.sync()
-        el_h = time.perf_counter() - t1
-        if world > 1:
-            dist.barrier()
-        live_h = np.arange(act.shape[2]) < counts[hs][..., None]
-        corr_h = int(np.count_nonzero(live_h & (act[hs] != 2)))
-        if world > 1:
-            el_h, corr_h, _ = reduce_ranks(el_h, corr_h, poses, be.device)
-        host_rate = {"value": corr_h / el_h, "unit": "corrections/s", "ms_per_step": el_h / K * 1e3,
-                     "note": "PCIe-inclusive: the same messages handed over as host arrays "
-                             "(ekf_replay: host planning, one descriptor upload, launches), "
-                             f"messages {hs.start}..{hs.stop - 1}; not the value"}
-    bytes_per_launch = ekf.sigma_pass_bytes()
-    avg_sig_s = ms_sig / max(n_sig, 1) / 1e3
-    achieved = bytes_per_launch / avg_sig_s / 1e9 if n_sig else 0.0
+    if args.full:
+        # ---- roofline pass: same work, Σ-pass launches bracketed by HIP events ----
+        ps = slice(t0s + K, t0s + 2 * K)
+        ekf.profile(True)
+        msgs(ps.start, ps.stop)
+        n_sig, ms_sig = ekf.profile_read(0)
+        n_gain, ms_gain = ekf.profile_read(1)
+        n_fac, ms_fac = ekf.profile_read(3)
+        n_res, ms_res = ekf.profile_read(4)
+        n_asc, ms_asc = ekf.profile_read(2)
+        ekf.profile(False)
+        live = np.arange(act.shape[2]) < counts[ps][..., None]
+        res_corr = int(np.count_nonzero(live & (act[ps] != 2)))
+        if inputs == "hbm":  # the same path fed host arrays (ekf_replay): host planning, PCIe timed
+            hs = slice(t0s + 2 * K, t0s + 3 * K)
+            ekf.sync()  # (the planning state comes back from the device first: not this span's cost)
+            if world > 1:
+                dist.barrier()
+            be.sync()
+            t1 = time.perf_counter()
+            msgs(hs.start, hs.stop, host=True)
+            be.sync()
+            el_h = time.perf_counter() - t1
+            if world > 1:
+                dist.barrier()
+            live_h = np.arange(act.shape[2]) < counts[hs][..., None]
+            corr_h = int(np.count_nonzero(live_h & (act[hs] != 2)))
+            if world > 1:
+                el_h, corr_h, _ = reduce_ranks(el_h, corr_h, poses, be.device)
+            host_rate = {"value": corr_h / el_h, "unit": "corrections/s",
+                         "ms_per_step": el_h / K * 1e3,
+                         "note": "PCIe-inclusive: the same messages handed over as host arrays "
+                                 "(ekf_replay: host planning, one descriptor upload, launches), "
+                                 f"messages {hs.start}..{hs.stop - 1}; not the value"}
+        bytes_per_launch = ekf.sigma_pass_bytes()
+        avg_sig_s = ms_sig / max(n_sig, 1) / 1e3
+        achieved = bytes_per_launch / avg_sig_s / 1e9 if n_sig else 0.0
 
-    if traffic and isinstance(traffic.get("mfma_busy"), dict) and n_sig:
-        # busy SIMD-cycles over what 1024 SIMDs offer in the event-timed launch at the 2.4 GHz
-        # maximum clock (the chip runs slower under load, so this is a lower bound)
-        mb = traffic["mfma_busy"]
-        mb["busy_frac_at_max_clock"] = mb["SQ_VALU_MFMA_BUSY_CYCLES"] / (avg_sig_s * 2.4e9 * 1024)
+        if traffic and isinstance(traffic.get("mfma_busy"), dict) and n_sig:
+            # busy SIMD-cycles over what 1024 SIMDs offer in the event-timed launch at the 2.4 GHz
+            # maximum clock (the chip runs slower under load, so this is a lower bound)
+            mb = traffic["mfma_busy"]
+            mb["busy_frac_at_max_clock"] = (mb["SQ_VALU_MFMA_BUSY_CYCLES"] /
+                                            (avg_sig_s * 2.4e9 * 1024))
     result = None
     if rank == 0:
         value = total_corr / elapsed
@@ -666,7 +722,16 @@ def run(args, rank, world, local, backend=None):
                        "inputs": inputs,
                        "parallelism": f"independent filters x{world} ranks",
                        "distributed": dist_info},
-            "roofline": {
+        }
+        result["region_end"] = {
+            "timed_until": "ekf_flush, then torch.cuda.synchronize (device-wide: the library's "
+                           "streams included)",
+            "library_sync_after_us": lib_sync_after_us}
+        if world > 1:
+            result["gathered_poses"] = {"filters": int(all_poses.shape[0]),
+                                        "all_finite": bool(np.all(np.isfinite(all_poses)))}
+        if args.full:
+            result["roofline"] = {
                 "kernel": "k_sigma_pass", "bound": "hbm", "achieved": achieved,
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                 "traffic": traffic["bytes_per_launch"] if traffic else None,
@@ -697,22 +762,14 @@ def run(args, rank, world, local, backend=None):
                     "ceiling_corrections_per_s": (HBM_PEAK_GBS * 1e9 / (passes * bytes_per_launch) * (
                         total_corr / world / K)) if bytes_per_launch else None,
                 },
-            },
-        }
-        result["roofline"]["end_to_end_frac"] = result["roofline"]["end_to_end"]["frac"]
-        result["region_end"] = {
-            "timed_until": "ekf_flush, then torch.cuda.synchronize (device-wide: the library's "
-                           "streams included)",
-            "library_sync_after_us": lib_sync_after_us}
-        if host_rate is not None:
-            result["host_inputs"] = host_rate
-        if n_asc:
-            result["roofline"]["assoc_kernel_avg_us"] = ms_asc / n_asc * 1e3
-            result["roofline"]["assoc_launches"] = n_asc
-        if world > 1:
-            result["gathered_poses"] = {"filters": int(all_poses.shape[0]),
-                                        "all_finite": bool(np.all(np.isfinite(all_poses)))}
-        if n_res:
+            }
+            result["roofline"]["end_to_end_frac"] = result["roofline"]["end_to_end"]["frac"]
+            if host_rate is not None:
+                result["host_inputs"] = host_rate
+            if n_asc:
+                result["roofline"]["assoc_kernel_avg_us"] = ms_asc / n_asc * 1e3
+                result["roofline"]["assoc_launches"] = n_asc
+        if args.full and n_res:
             # resident path (ekf_resident.hip): one launch runs the whole replay, Σ in registers;
             # its bound is the sequential f64 chain of one CU per filter, priced against that
             # CU's share of the fp64 vector peak (78.6 TF / 256 CUs)
@@ -736,15 +793,15 @@ def run(args, rank, world, local, backend=None):
     # handles, then messages t0s..) or the one read before the last warm-up messages (t_ws..)
     ws = warm_state[0] if warm_state else ws0
     tp = t0s if warm_state else t_ws
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         result["parity"] = parity(args, N, ekf_first_poses(args, be, N, dtype, ws, counts, ids,
                                                            act, rel, odom, tp, local,
                                                            gpu_in=gpu_in),
                                   ws, counts, ids, act, rel, odom, tp)
         if world == 1:
             result["cpu_baseline"] = cpu_baseline(args, N, ws, counts, ids, act, rel, odom, tp)
-    if (rank == 0 and world == 1 and args.workload == "n1024_fp32" and gpu_in is not None
-            and warm_state and not args.no_fp64):
+    if (rank == 0 and world == 1 and args.full and args.workload == "n1024_fp32"
+            and gpu_in is not None and warm_state and not args.no_fp64):
         result["fp64"] = fp64_leg(args, be, N, warm_state[0], gpu_rows, ids.shape[2], n_warm, W, K,
                                   local, counts, ids, act, rel, odom, gpu_in)
     if rank == 0:

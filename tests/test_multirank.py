@@ -99,7 +99,7 @@ def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK="0")
     args = bench.parse(["--workload", "tiny", "--gpus", str(world), "--steps", "3",
-                        "--warmup", "2", "--traffic", "off", "--parity-messages", "2"])
+                        "--warmup", "2", "--full", "--traffic", "off", "--parity-messages", "2"])
     try:
         result, poses = bench.run(args, rank, world, 0, CpuBackend())
     except BaseException as e:  # report at once instead of leaving the parent to time out

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for i in $(seq 1 $R); do
   for side in A B; do
     envs=$A; [ $side = B ] && envs=$B
-    env $envs timeout -k 10 300 python -u bench.py --no-cpu --traffic off --no-fp64 "$@" \
+    env $envs timeout -k 10 300 python -u bench.py --full --no-cpu --traffic off --no-fp64 "$@" \
       > gpurun_out/${tag}_${side}${i}.json 2> gpurun_out/${tag}_${side}${i}.err || exit $?
     python - "$side" "$i" "gpurun_out/${tag}_${side}${i}.json" <<'PY'
 import json, sys

@@ -13,7 +13,7 @@ tail -2 gpurun_out/${tag}_gpu_tests.log
 grep FAILED gpurun_out/${tag}_gpu_tests.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 for w in n1024_fp32_assoc n1024_fp64_assoc; do
-  timeout -k 10 400 python -u bench.py --workload $w --steps 20 --warmup 5 \
+  timeout -k 10 400 python -u bench.py --full --workload $w --steps 20 --warmup 5 \
     > gpurun_out/${tag}_${w}_s20.json 2> gpurun_out/${tag}_${w}_s20.err || exit 3
   python -c "import json; d=json.load(open('gpurun_out/${tag}_${w}_s20.json')); r=d['roofline']; print('$w', '%.4g' % d['value'], round(d['ms_per_step']*1e3,2), 'us/step; pass', round(r['avg_launch_us'],2), 'frac', round(r['frac'],3), 'traffic', r.get('traffic'), 'cpu', (d.get('cpu_baseline') or {}).get('value'), 'parity', d.get('parity',{}).get('pose_rmse_m'))"
 done

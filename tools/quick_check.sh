@@ -16,7 +16,7 @@ if [ "$expr" != "none" ]; then
 fi
 for K in 20 200; do
   W=$(( K == 20 ? 5 : 20 ))
-  timeout -k 10 300 python -u bench.py --steps $K --warmup $W --no-cpu --traffic off "$@" \
+  timeout -k 10 300 python -u bench.py --full --steps $K --warmup $W --no-cpu --traffic off "$@" \
     > gpurun_out/${tag}_s$K.json 2> gpurun_out/${tag}_s$K.err || exit $?
   python3 - "$tag" "$K" <<'EOF'
 import json, sys
