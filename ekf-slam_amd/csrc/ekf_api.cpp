@@ -112,6 +112,8 @@ struct ekf_ctx {
   std::vector<Pose2> odom;
   std::vector<int> parity;
   std::vector<char> pending;
+  std::vector<unsigned> held;    // status bits taken off the device word by the synchronous forms
+                                 // (take_numeric); ekf_get_status reports and clears them too
   std::vector<int> prev_m;       // ≥ 0: last chunk was a pipelined pair (its record is valid)
   std::vector<std::array<int, kMaxChunk>> prev_ids;  // that chunk's landmark ids
   std::vector<std::array<long, 2>> stg_desc;  // plan_d indices of its last two pipelined chunks
@@ -555,6 +557,7 @@ int ensure_am(ekf_ctx* h) {
   b.cur_stride = (kMaxChunk + 1) * Np;
   b.gran_stride = static_cast<size_t>(kMaxChunk + 1) * G * 4;
   b.xcd = h->am_route == EKF_ASSOC_CHUNK_XCD ? 1 : 0;
+  b.prior = h->cfg.init_var;
   b.spin = 1u << 22;  // ≈ 0.1 s of polls per exchange
   if (const char* e = std::getenv("EKF_AM_SPIN_LOG2")) b.spin = 1u << std::min(std::atoi(e), 30);
   if (const char* e = std::getenv("EKF_AM_DROP")) b.drop = std::atoi(e) != 0 ? 1 : 0;
@@ -958,6 +961,33 @@ int load_batch(ekf_ctx* h, int assoc_mode, int m_max, const int* counts, const i
 
 bool valid(ekf_ctx* h, int f) { return h && f >= 0 && f < h->F; }
 
+// The device's status word only accumulates (atomicOr), so a set EKF_FLAG_NUMERIC cannot show a
+// second skip. The synchronous association forms therefore move that bit into a host-side word
+// (reported and cleared by ekf_get_status like the device's): once before their own work, so that
+// a skip of an earlier asynchronous call is not charged to them, and once after it, which tells
+// whether this call skipped a marker (the oracle's -4). The device must be drained.
+// *fl: the device word as read (nullable).
+int take_numeric(ekf_ctx* h, int f, unsigned* fl_out) {
+  unsigned fl = 0;
+  HIPCHK(hipMemcpy(&fl, &h->ctl[f].status, sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (fl & EKF_FLAG_NUMERIC) {
+    const unsigned rest = fl & ~EKF_FLAG_NUMERIC;
+    HIPCHK(hipMemcpy(&h->ctl[f].status, &rest, sizeof(unsigned), hipMemcpyHostToDevice));
+    h->held[f] |= EKF_FLAG_NUMERIC;
+  }
+  if (fl_out) *fl_out = fl;
+  return EKF_OK;
+}
+
+// After a synchronous form's drain: EKF_E_RANGE while the filter's status holds EKF_FLAG_RANGE
+// (`range`: ekf_sensor), else EKF_E_NUMERIC if this call set EKF_FLAG_NUMERIC.
+int status_rc(ekf_ctx* h, int f, bool range) {
+  unsigned fl = 0;
+  if (int rc = take_numeric(h, f, &fl)) return rc;
+  if (range && (fl & EKF_FLAG_RANGE)) return EKF_E_RANGE;
+  return (fl & EKF_FLAG_NUMERIC) ? EKF_E_NUMERIC : EKF_OK;
+}
+
 }  // namespace
 
 namespace ekfslam {
@@ -1081,6 +1111,7 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
   h->odom.assign(h->F, Pose2{});
   h->parity.assign(h->F, 0);
   h->pending.assign(h->F, 0);
+  h->held.assign(h->F, 0);
   h->prev_m.assign(h->F, -1);
   h->stg_desc.assign(h->F, std::array<long, 2>{-1L, -1L});
   h->prev_ids.assign(h->F, std::array<int, kMaxChunk>{});
@@ -1285,16 +1316,13 @@ int ekf_sensor(ekf_t h, int f, int m, const double* rel_xy, int* assoc_out, int*
     plan_unknown(h, f, 1, true, true, 0, m);
     return submit(h);
   }
+  if (int r0 = settle(h)) return r0;  // earlier (asynchronous) skips are not this call's
+  if (int r0 = take_numeric(h, f, nullptr)) return r0;
   const int rc = assoc_sync(h, f, 1, true, true, m, assoc_out, is_new_out);
   if (rc) return rc;
-  {
-    unsigned fl = 0;
-    if (drain(h)) return EKF_E_HIP;
-    if (int t = take_fatal(h)) return t;
-    HIPCHK(hipMemcpy(&fl, &h->ctl[f].status, sizeof(unsigned), hipMemcpyDeviceToHost));
-    if (fl & EKF_FLAG_RANGE) return EKF_E_RANGE;
-  }
-  return EKF_OK;
+  if (drain(h)) return EKF_E_HIP;
+  if (int t = take_fatal(h)) return t;
+  return status_rc(h, f, true);
 }
 
 int ekf_batch_sensor(ekf_t h, int assoc_mode, int m_max, const int* counts, const int* ids,
@@ -1493,13 +1521,16 @@ int ekf_associate_correct(ekf_t h, int f, double rx, double ry, int* j, int* is_
   mk.push_back(k);
   hipSetDevice(h->cfg.device);
   int jj = -1, nn = 0;
+  if (int r0 = settle(h)) return r0;  // earlier (asynchronous) skips are not this call's
+  if (int r0 = take_numeric(h, f, nullptr)) return r0;
   const int rc = assoc_sync(h, f, 1, false, false, 1, &jj, &nn);
   if (rc) return rc;
   if (int t = take_fatal(h)) return t;  // (assoc_sync drained)
   if (j) *j = jj;
   if (is_new) *is_new = nn;
+  const int nrc = status_rc(h, f, false);
   if (jj < 0) return EKF_E_RANGE;
-  return EKF_OK;
+  return nrc;
 }
 
 int ekf_posterior(ekf_t h, int f) {
@@ -1572,6 +1603,7 @@ int ekf_reset(ekf_t h, int f) {
   for (int k = f0; k < f0 + nf; ++k) {
     h->parity[k] = 0;
     h->pending[k] = 0;
+    h->held[k] = 0;
     h->prev_m[k] = -1;
     forget_desc(h, k);
   }
@@ -1669,6 +1701,8 @@ int ekf_get_status(ekf_t h, int f, unsigned* flags) {
   HIPCHK(hipMemcpy(flags, &h->ctl[f].status, sizeof(unsigned), hipMemcpyDeviceToHost));
   const unsigned z = 0;
   HIPCHK(hipMemcpy(&h->ctl[f].status, &z, sizeof(unsigned), hipMemcpyHostToDevice));
+  *flags |= h->held[f];
+  h->held[f] = 0;
   return EKF_OK;
 }
 

@@ -637,6 +637,10 @@ __global__ __launch_bounds__(kAmThreads) void k_assoc_msg(PassArgs<T> A, AmArgs 
       for (int t = 0; t < 6; ++t) jpk[t] = sh.jc[10 + t];
       xj[0] = isnew ? nx : sh.jc[16];
       xj[1] = isnew ? ny : sh.jc[17];
+      // fp32 Σ: a mapped landmark still at its prior variance (committed by a marker whose
+      // correction was skipped, so never corrected) cancels 1e7 − (1e7 − δ) like a first sighting:
+      // the chunk's block is patched for it too (uniform: every workgroup reads the same block)
+      if (sizeof(T) == 4 && (jkk[0] >= 0.5 * B.prior || jkk[3] >= 0.5 * B.prior)) any_new = true;
       double zhat[2], braw;
       bool bok;
       range_bearing(pose, xj[0], xj[1], zhat, H0, H1, &braw, &bok);

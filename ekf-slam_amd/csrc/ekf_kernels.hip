@@ -392,6 +392,9 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
           Si[0] = Si[1] = Si[2] = Si[3] = 0.0;
           nv0 = nv1 = 0.0;
           ka = kb = mm0 = mm1 = 0.0;
+          // ... and S itself (non-finite here): the Joseph form's V = Σ·Hᵀ − K·S below must come
+          // out 0 like K, not 0·NaN
+          for (int k = 0; k < 4; ++k) Sm_keep[k] = 0.0;
         }
       }
     }

@@ -94,6 +94,8 @@ struct AmArgs {
   unsigned spin;  // bounded polls per exchange (EKF_FLAG_TIMEOUT beyond; EKF_AM_SPIN_LOG2)
   int drop;       // fault injection (EKF_AM_DROP=1, tests only): the last workgroup never
                   // publishes its first exchange, so every workgroup's poll times out
+  double prior;   // the landmark prior variance (ekf_config::init_var): fp32 Σ patches the block of
+                  // a landmark that is still at it when a marker corrects it
 };
 // Workgroups of k_assoc_msg one CU holds at once (its LDS bounds it), for the co-residency check:
 // a filter's G workgroups spin on each other, so all of them must fit the bulk stream's CUs

@@ -24,7 +24,14 @@ extern "C" {
                               Armadillo bounds check throws (slam.cpp:213, :351) */
 #define EKF_E_EMPTY (-3)   /* empty MarkerArray: the reference throws at msg.markers.at(0)
                               (slam.cpp:281, :498) */
-#define EKF_E_NUMERIC (-4) /* singular or non-finite innovation covariance S (slam.cpp:252) */
+#define EKF_E_NUMERIC (-4) /* singular or non-finite innovation covariance S (slam.cpp:252): that
+                              marker's correction was skipped (a first sighting keeps its landmark
+                              and counter). Returned by the synchronous forms only — ekf_sensor and
+                              ekf_associate_correct with decision outputs — by every call that
+                              skipped a marker itself (skips of earlier asynchronous calls are not
+                              charged to it); EKF_E_RANGE takes precedence when both apply. Every
+                              asynchronous form reports a skip through EKF_FLAG_NUMERIC alone;
+                              ekf_get_status shows the flag after either kind of call. */
 #define EKF_E_HIP (-5)     /* HIP runtime error */
 #define EKF_E_NOMEM (-6)
 #define EKF_E_TIMEOUT (-7) /* a device hand-off (cross-stream epoch or k_assoc_msg's exchange
@@ -126,7 +133,10 @@ int ekf_fake_sensor(ekf_t h, int filter, int m, const int* ids, const int* actio
 
 /* Slam::sensor_cb (slam.cpp:318-530) minus ROS publishing: predict, then per marker the
  * Mahalanobis nearest-neighbour association (:344-440) and the correction (:443-488).
- * If assoc_out/is_new_out are non-NULL the call synchronises and returns the decisions. */
+ * If assoc_out/is_new_out are non-NULL the call synchronises and returns the decisions, and
+ * EKF_E_RANGE (a marker met a full map) or else EKF_E_NUMERIC (a marker's correction was skipped)
+ * as the oracle's sensor_cb does; without outputs it is asynchronous and both are reported through
+ * ekf_get_status only. */
 int ekf_sensor(ekf_t h, int filter, int m, const double* rel_xy, int* assoc_out,
                int* is_new_out);
 
@@ -163,7 +173,8 @@ int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int*
 int ekf_predict(ekf_t h, int filter);
 /* One known-association correction (slam.cpp:207-268), predict folded in if pending. */
 int ekf_correct(ekf_t h, int filter, int landmark_id, double rel_x, double rel_y);
-/* One association + correction (slam.cpp:345-488). Synchronous when j/is_new non-NULL. */
+/* One association + correction (slam.cpp:345-488). Synchronous when j/is_new non-NULL: then
+ * EKF_E_RANGE (map full, *j = -1) or else EKF_E_NUMERIC (this marker's correction was skipped). */
 int ekf_associate_correct(ekf_t h, int filter, double rel_x, double rel_y, int* j, int* is_new);
 /* Posterior (slam.cpp:273-291): t_map_odom = T(x, y, θ)·t_odom_robot⁻¹. */
 int ekf_posterior(ekf_t h, int filter);

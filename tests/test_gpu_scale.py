@@ -48,8 +48,18 @@ ERRORS = {}
 @pytest.fixture(scope="module", autouse=True)
 def _record_errors():
     yield
+    _write_errors()
+
+
+def errors_dir():
+    """The directory the suite's measured errors go to (tests/edge_scenarios.py writes there too)."""
     out = os.path.join(os.environ.get("GRAFT_REPO_ROOT", "."), "gpurun_out")
     os.makedirs(out, exist_ok=True)
+    return out
+
+
+def _write_errors():
+    out = errors_dir()
     with open(os.path.join(out, "scale_errors.json"), "w") as fh:
         json.dump(ERRORS, fh, indent=1)
 
