@@ -85,11 +85,6 @@ struct ekf_ctx {
   unsigned* sync = nullptr;               // device epochs: Σ pass done, its ticket, chains done
   hipEvent_t ev_sig[2] = {nullptr, nullptr};  // bulk → main: Σ pass of launch s, by s & 1
   long long seq = 0;                      // launch pairs issued
-  // dev only (EKF_DBG_ORDER bit mask, tools/diag_handover.py): conservative hand-off variants
-  // for locating a missing ordering edge of the event schedule
-  unsigned dbg_order = 0;
-  std::vector<hipEvent_t> dbg_ev;         // bit 4: a fresh event per Σ pass (never re-recorded)
-  unsigned long long* dlog = nullptr;     // bit 4096: PassArgs::dlog
   void* sig[2] = {nullptr, nullptr};
   double* x[2] = {nullptr, nullptr};
   void* kcat = nullptr;
@@ -173,8 +168,6 @@ PassArgs<T> args(ekf_ctx* h, const MsgDesc* desc, int f0) {
   a.r = h->cfg.r_noise;
   a.gate = h->cfg.mah_gate;
   a.joseph = h->joseph ? 1 : 0;
-  a.dbg = static_cast<int>(h->dbg_order >> 8);
-  a.dlog = h->dlog;
   return a;
 }
 
@@ -235,6 +228,13 @@ int join_bulk(ekf_ctx* h) {
   return EKF_OK;
 }
 
+// Bulk waits for everything issued to the main stream so far.
+int fork_bulk(ekf_ctx* h) {
+  HIPCHK(hipEventRecord(h->ev_chain, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->bulk, h->ev_chain, 0));
+  return EKF_OK;
+}
+
 // The main stream runs the chains back to back; the bulk stream runs each chunk's factors and Σ
 // pass. With disjoint CU masks (devsync) the two streams synchronise on the device only: a chain
 // polls the Σ-pass epoch (it needs the pass two launches back: Σ_in and x of the chunk before the
@@ -269,30 +269,17 @@ int launch_group(ekf_ctx* h, const MsgDesc* dptr, const MsgDesc* hd, int f0, int
   }
   if (pipelined && !nolook) {
     // events: a rebuilding (kLook) chain needs the Σ pass two launches back
-    if (!h->devsync) {
-      if (h->dbg_order & 1u) {
-        if (join_bulk(h)) return EKF_E_HIP;
-      } else if (h->dbg_order & 16u) {
-        if (s0 >= 2 && s0 - 2 < h->dbg_ev.size())
-          HIPCHK(hipStreamWaitEvent(ms, h->dbg_ev[s0 - 2], 0));
-      } else {
-        HIPCHK(hipStreamWaitEvent(ms, h->ev_sig[s0 & 1], 0));
-      }
-    }
+    if (!h->devsync) HIPCHK(hipStreamWaitEvent(ms, h->ev_sig[s0 & 1], 0));
   } else if (!a.polls) {
     // a chain that gathers its own Σ_in needs the previous pass: everything on the bulk stream
     if (join_bulk(h)) return EKF_E_HIP;
   }
-  if (h->dbg_order & 8192u) HIPCHK(launch_dbg_sum<T>(a, nf, 3, ms));
   int rc = timed(h, 1, ms, [&](hipEvent_t e0, hipEvent_t e1) {
     return launch_chain<T>(a, nf, nchunks, ms, e0, e1);
   });
   if (rc) return rc;
   if (h->prof) h->prof_chunks += nchunks;
-  if (two && !h->devsync) {  // nchunks == 1 here
-    HIPCHK(hipEventRecord(h->ev_chain, ms));
-    HIPCHK(hipStreamWaitEvent(bs, h->ev_chain, 0));
-  }
+  if (two && !h->devsync && fork_bulk(h)) return EKF_E_HIP;  // nchunks == 1 here
   for (int i = 0; i < nchunks; ++i) {
     PassArgs<T> ai = a;
     ai.desc = dptr + static_cast<size_t>(i) * nf;
@@ -307,7 +294,6 @@ int launch_group(ekf_ctx* h, const MsgDesc* dptr, const MsgDesc* hd, int f0, int
       return launch_factors<T>(ai, nf, bs, e0, e1);
     });
     if (rc) return rc;
-    if (h->dbg_order & 8192u) HIPCHK(launch_dbg_sum<T>(ai, nf, 1, bs));
     // some filter stages the rebuild operands of its chunk after next (device-written descriptors:
     // the caller's hint — the group's first stage_hint chunks may, the last two of a device replay
     // have no chunk after next in it — the staging kernel reads every descriptor's own flags)
@@ -321,20 +307,7 @@ int launch_group(ekf_ctx* h, const MsgDesc* dptr, const MsgDesc* hd, int f0, int
       return launch_sigma_pass<T>(ai, nf, last ? publish_end : !in_group, stage, bs, e0, e1);
     });
     if (rc) return rc;
-    if (h->dbg_order & 8192u) HIPCHK(launch_dbg_sum<T>(ai, nf, 2, bs));
     if (!h->devsync) HIPCHK(hipEventRecord(h->ev_sig[(s0 + i) & 1], bs));
-    if (h->dbg_order & 16u) {
-      while (h->dbg_ev.size() <= s0 + i) {
-        hipEvent_t e = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->dbg_ev.push_back(e);
-      }
-      HIPCHK(hipEventRecord(h->dbg_ev[s0 + i], bs));
-    }
-    if ((h->dbg_order & 8u) && !h->devsync) {  // every launch pair drained before the next
-      HIPCHK(hipStreamSynchronize(bs));
-      HIPCHK(hipStreamSynchronize(ms));
-    }
   }
   h->seq += nchunks;
   h->epoch_owed = a.polls && !publish_end;
@@ -409,20 +382,16 @@ int drain(ekf_ctx* h) {
 // devsync: k_assoc waits on the device for the last Σ pass (its epoch is h->seq) instead of the
 // main stream joining the bulk stream first
 int assoc(ekf_ctx* h, const MsgDesc* dptr, int f0, int nf, bool poll) {
-  if (h->cfg.dtype == EKF_F32) {
-    PassArgs<float> a = args<float>(h, dptr, f0);
+  auto run = [&](auto tag) -> int {
+    using T = decltype(tag);
+    PassArgs<T> a = args<T>(h, dptr, f0);
     a.polls = poll ? 1 : 0;
     a.need_sigma = poll ? static_cast<unsigned>(h->seq) : 0u;
     return timed(h, 2, h->stream, [&](hipEvent_t e0, hipEvent_t e1) {
-      return launch_assoc<float>(a, nf, h->stream, e0, e1);
+      return launch_assoc<T>(a, nf, h->stream, e0, e1);
     });
-  }
-  PassArgs<double> a = args<double>(h, dptr, f0);
-  a.polls = poll ? 1 : 0;
-  a.need_sigma = poll ? static_cast<unsigned>(h->seq) : 0u;
-  return timed(h, 2, h->stream, [&](hipEvent_t e0, hipEvent_t e1) {
-    return launch_assoc<double>(a, nf, h->stream, e0, e1);
-  });
+  };
+  return h->cfg.dtype == EKF_F32 ? run(float{}) : run(double{});
 }
 
 // Known association, one message per filter in [f0, f0+nf): msgs[k] holds filter f0+k's markers.
@@ -649,8 +618,7 @@ int assoc_msg_group(ekf_ctx* h, const MsgDesc* dptr, int f0, int nf, bool publis
   if (int rc = ensure_am(h)) return rc;
   hipStream_t bs = h->serial ? h->stream : h->bulk;
   if (!h->serial && h->main_dirty) {
-    HIPCHK(hipEventRecord(h->ev_chain, h->stream));
-    HIPCHK(hipStreamWaitEvent(h->bulk, h->ev_chain, 0));
+    if (fork_bulk(h)) return EKF_E_HIP;
     h->main_dirty = false;
     h->main_unordered = false;
   }
@@ -799,8 +767,7 @@ int flush(ekf_ctx* h) {
   if (join_bulk(h)) return EKF_E_HIP;  // the bulk stream may still read descriptors
   HIPCHK(hipMemcpyAsync(h->ddesc, sl.p, nd * sizeof(MsgDesc), hipMemcpyHostToDevice, h->stream));
   // the bulk stream reads these descriptors too: one main → bulk hop per upload
-  HIPCHK(hipEventRecord(h->ev_chain, h->stream));
-  HIPCHK(hipStreamWaitEvent(h->bulk, h->ev_chain, 0));
+  if (fork_bulk(h)) return EKF_E_HIP;
   h->main_dirty = false;
   h->main_unordered = false;
   HIPCHK(hipEventRecord(sl.ev, h->stream));
@@ -1123,7 +1090,6 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
   };
   if (hipSetDevice(cfg.device) != hipSuccess) return fail(EKF_E_HIP);
   if (const char* e = std::getenv("EKF_SERIAL")) h->serial = std::atoi(e) != 0;
-  if (const char* e = std::getenv("EKF_DBG_ORDER")) h->dbg_order = static_cast<unsigned>(std::atoi(e));
   if (const char* e = std::getenv("EKF_ASSOC_MSG")) h->assoc_msg = std::atoi(e) != 0;
   {  // EKF_RESIDENT=0: the HBM pipeline at every size (tests compare the two)
     const char* e = std::getenv("EKF_RESIDENT");
@@ -1175,13 +1141,7 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
     if (hipMalloc(&h->stage, stage_bytes) != hipSuccess) return fail(EKF_E_NOMEM);
     if (hipMemset(h->stage, 0, stage_bytes) != hipSuccess) return fail(EKF_E_HIP);
   }
-  // (+ 3F words: PassArgs::dbg & 8's per-kernel launch epochs)
-  if (h->dbg_order & (4096u | 8192u)) {
-    const size_t b = sizeof(unsigned long long) * kDlogKinds * 64 * 64 * 8;
-    if (hipMalloc(&h->dlog, b) != hipSuccess) return fail(EKF_E_NOMEM);
-    if (hipMemset(h->dlog, 0, b) != hipSuccess) return fail(EKF_E_HIP);
-  }
-  const size_t sync_bytes = sizeof(unsigned) * (kSyncChain + 4 * static_cast<size_t>(h->F));
+  const size_t sync_bytes = sizeof(unsigned) * (kSyncChain + static_cast<size_t>(h->F));
   if (hipMalloc(&h->sync, sync_bytes) != hipSuccess) return fail(EKF_E_NOMEM);
   if (hipMemset(h->sync, 0, sync_bytes) != hipSuccess) return fail(EKF_E_HIP);
   h->ddesc_cap = std::max(kDescInit, static_cast<size_t>(h->F) * 4);
@@ -1248,10 +1208,8 @@ int ekf_destroy(ekf_t h) {
   if (h->ev_chain) hipEventDestroy(h->ev_chain);
   if (h->ev_join) hipEventDestroy(h->ev_join);
   if (h->sync) hipFree(h->sync);
-  if (h->dlog) hipFree(h->dlog);
   for (hipEvent_t e : h->ev_sig)
     if (e) hipEventDestroy(e);
-  for (hipEvent_t e : h->dbg_ev) hipEventDestroy(e);
   if (h->bulk) hipStreamDestroy(h->bulk);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -1412,15 +1370,13 @@ int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int*
   // starts beside the planner instead of behind a main → bulk event hop (≈ 6 µs of each replay)
   const bool beside = h->devsync && !h->serial;
   // the bulk stream may still read the last descriptors (an idle one reads nothing: no hop)
-  if (((h->dbg_order & 2u) || hipStreamQuery(h->bulk) != hipSuccess) && join_bulk(h))
-    return EKF_E_HIP;
+  if (hipStreamQuery(h->bulk) != hipSuccess && join_bulk(h)) return EKF_E_HIP;
   // ... and the main stream: work there that the bulk stream is not ordered after (a k_posterior
   // of ekf_posterior reads its descriptor in ddesc) must end before a planner on the bulk stream
   // rewrites ddesc. (Chains are covered: the bulk stream's factor kernels follow every chain
   // through its epoch or an event, so a planner enqueued behind them runs after it.)
   if (beside && h->main_unordered) {
-    HIPCHK(hipEventRecord(h->ev_chain, h->stream));
-    HIPCHK(hipStreamWaitEvent(h->bulk, h->ev_chain, 0));
+    if (fork_bulk(h)) return EKF_E_HIP;
     h->main_unordered = false;
   }
   hipStream_t ps = beside ? h->bulk : h->stream;
@@ -1465,8 +1421,7 @@ int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int*
   } else {
     // the bulk stream reads these descriptors too: one main → bulk hop (recorded before the
     // chain: behind a persistent chain launch the bulk kernels it waits for could never start)
-    HIPCHK(hipEventRecord(h->ev_chain, h->stream));
-    HIPCHK(hipStreamWaitEvent(h->bulk, h->ev_chain, 0));
+    if (fork_bulk(h)) return EKF_E_HIP;
   }
   h->main_dirty = false;
   const bool stg = h->stage != nullptr;
@@ -1484,7 +1439,6 @@ int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int*
                  stg && t + 2 < T ? 1 : 0);
   }
   h->main_dirty = true;
-  if (!rc && (h->dbg_order & 32u) && drain(h)) return EKF_E_HIP;
   return rc;
 }
 
@@ -1750,7 +1704,7 @@ int ekf_debug_poison_lds(int device) {
 }
 
 #ifdef EKF_DIAG_STAMPS
-int ekfslam_diag_read_stamps(unsigned long long* out, int n);  // ekf_kernels.hip
+int ekfslam_diag_read_stamps(unsigned long long* out, int n);  // ekf_chain.hip
 // dev only (libekfslam_diag.so): the chain kernel's s_memtime stamps of filter 0's last chunk
 int ekf_diag_stamps(unsigned long long* out, int n) { return ekfslam_diag_read_stamps(out, n); }
 int ekfslam_res_read_stamps(unsigned long long* out, int n);  // ekf_resident.hip
@@ -1760,23 +1714,6 @@ extern "C" int ekfslam_diag_read_am_stamps(unsigned long long* out);  // ekf_ass
 // dev only: k_assoc_msg's s_memrealtime stamps, [2 workgroups][kMaxChunk + 1][8]
 int ekf_diag_am_stamps(unsigned long long* out) { return ekfslam_diag_read_am_stamps(out); }
 #endif
-
-// dev only (tools/diag_handover.py): the PassArgs::dbg & 4 counters, sync[kSyncDbg + i], i < n ≤ 16
-int ekf_debug_counters(ekf_t h, unsigned* out, int n) {
-  if (!h || !out || n < 0 || n > 16) return EKF_E_ARG;
-  if (int rc = settle(h)) return rc;
-  HIPCHK(hipMemcpy(out, h->sync + kSyncDbg, n * sizeof(unsigned), hipMemcpyDeviceToHost));
-  return EKF_OK;
-}
-
-// dev only: the PassArgs::dlog checksums (EKF_DBG_ORDER & 4096), kDlogKinds·64·64·8 words
-int ekf_debug_log(ekf_t h, unsigned long long* out) {
-  if (!h || !out || !h->dlog) return EKF_E_ARG;
-  if (int rc = settle(h)) return rc;
-  HIPCHK(hipMemcpy(out, h->dlog, sizeof(unsigned long long) * kDlogKinds * 64 * 64 * 8,
-                   hipMemcpyDeviceToHost));
-  return EKF_OK;
-}
 
 double ekf_sigma_pass_bytes(ekf_t h, int nf) {
   if (!h) return 0.0;

@@ -23,13 +23,17 @@
 //     crosses with each lane's landmark are gathered from Σ_in; every workgroup then forms the same
 //     S, S⁻¹, ν, K[pose], M[pose] and each lane its own K[k], M[k] — the chunk's Kcat / Mcat rows
 //     for the Σ pass — and applies the step to its block and state.
-// The Σ pass (k_sigma_pass, ekf_kernels.hip) then applies Σ_out = Σ_in + Q̄ − Kcatᵀ·Mcat once.
+// The Σ pass (k_sigma_pass, ekf_sigma_pass.hip) then applies Σ_out = Σ_in + Q̄ − Kcatᵀ·Mcat once.
 // fp32 Σ: a chunk that commits a new landmark also writes the final Σ[U, U] in fp64 (ChunkRec::Pend,
 // the first sighting's 1e7 − (1e7 − δ), slam.cpp:130) for k_patch_stage, after a last exchange.
 //
 // In exact arithmetic this equals the reference's sequential dense algebra; the decisions are the
 // reference's (tests/test_gpu_scale.py: every decision equal to the oracle's, new and known
 // landmarks, a marker 3e-4 from the gate).
+//
+// The file's end holds the other unknown-association kernel, k_assoc: one marker per launch, each
+// followed by a single-marker chunk (chain, factors, Σ pass) — the route the host takes when
+// k_assoc_msg's workgroups cannot all be resident (ekf_api.cpp am_route) or with EKF_ASSOC_MSG=0.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -360,14 +364,6 @@ __device__ __forceinline__ void hist_fma(const HistOps<J>& p, double (&acc)[8]) 
     acc[6] = fma(jv3, ok1, fma(jv2, ok0, acc[6]));
     acc[7] = fma(jv3, ok3, fma(jv2, ok2, acc[7]));
   }
-}
-
-// Workgroup barrier ordering LDS only: the waves' global stores (tables, Kcat / Mcat rows) are not
-// waited for here (__syncthreads' workgroup fence would drain them at every step).
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // Waves 1 (par 0) and 2 (par 1): per step, after wave 0 has published j (sh.jl) and j's history
@@ -1024,11 +1020,8 @@ template <typename T>
 hipError_t launch_assoc_msg(const PassArgs<T>& a, const AmArgs& b, int nf, hipStream_t s,
                             hipEvent_t e0, hipEvent_t e1) {
   const dim3 grid(b.xcd ? 8 * b.G : b.G, nf);
-  auto k = a.joseph ? k_assoc_msg<T, true> : k_assoc_msg<T, false>;
-  if (e0 && e1)
-    hipExtLaunchKernelGGL(k, grid, dim3(kAmThreads), 0, s, e0, e1, 0, a, b);
-  else
-    hipLaunchKernelGGL(k, grid, dim3(kAmThreads), 0, s, a, b);
+  launch(a.joseph ? k_assoc_msg<T, true> : k_assoc_msg<T, false>, grid, dim3(kAmThreads), s, e0, e1,
+         a, b);
   return hipGetLastError();
 }
 
@@ -1044,5 +1037,130 @@ template hipError_t launch_assoc_msg<double>(const PassArgs<double>&, const AmAr
                                              hipStream_t, hipEvent_t, hipEvent_t);
 template hipError_t launch_assoc_msg<float>(const PassArgs<float>&, const AmArgs&, int, hipStream_t,
                                             hipEvent_t, hipEvent_t);
+
+// ---- association of one marker per launch (k_assoc) -------------------------------------------
+// slam.cpp:344-440 for the marker in desc.z[0]: d_k = νᵀψ_k⁻¹ν over the known landmarks k < counter
+// (predict folded in when pending), the new slot's d forced to the gate (:406-408), first-index
+// argmin (arma::index_min), then commit (new landmark written into x_in, counter++) or roll back.
+constexpr int kAssocThreads = 1024;  // one known landmark per lane up to counter 1024: the gathers
+                                     // of every landmark in flight in one round
+template <typename T>
+__global__ __launch_bounds__(kAssocThreads) void k_assoc(PassArgs<T> A) {
+  __shared__ double s_pose[3], s_a[2], s_P33[3][3];
+  __shared__ double s_bd[kAssocThreads / 64];
+  __shared__ int s_bk[kAssocThreads / 64];
+  __shared__ int s_abort;
+  const MsgDesc& d = A.desc[blockIdx.y];
+  if (!(d.flags & kActive) || d.m == 0) return;
+  const int f = A.f0 + blockIdx.y;
+  const int tid = threadIdx.x;
+  const int ld = A.ld;
+  const T* S = A.sig[d.parity] + f * A.sig_stride;
+  double* x = A.x[d.parity] + f * A.x_stride;
+  FilterCtl* ctl = A.ctl + f;
+  // device epochs: Σ_in and x are the last Σ pass's (bulk stream), its epoch A.need_sigma
+  if (A.polls && A.need_sigma) {
+    if (tid == 0 && !epoch_wait_acquire(A.sync + kSyncSigma, A.need_sigma))
+      flag_timeout(&ctl->status, A.fatal);
+    __syncthreads();
+  }
+  const unsigned s = ctl->counter;
+  const int slot = d.assoc_slot;
+  if (tid == 0) {
+    double a1, a2;
+    predicted_pose(ctl->tmo, d, x, s_pose, &a1, &a2);
+    s_a[0] = a1;
+    s_a[1] = a2;
+    double raw[3][3];
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) raw[a][b] = static_cast<double>(S[a * ld + b]);
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        const double aa = (d.flags & kFirst) ? alpha_of(a, a1, a2) : 0.0;
+        const double ab = (d.flags & kFirst) ? alpha_of(b, a1, a2) : 0.0;
+        double v = raw[a][b] + aa * raw[0][b];
+        v = v + (raw[a][0] + aa * raw[0][0]) * ab;
+        if ((d.flags & kFirst) && a == b) v += A.q;
+        s_P33[a][b] = v;
+      }
+    s_abort = 0;
+    if (s >= static_cast<unsigned>(A.N)) {  // the reference indexes state(3+2·counter) out of range
+      s_abort = 1;
+      atomicOr(&ctl->status, EKF_FLAG_RANGE_D);
+      ctl->assoc_j[slot] = -1;
+      ctl->assoc_new[slot] = 0;
+    }
+  }
+  __syncthreads();
+  if (s_abort) return;
+  const double z0 = d.z[0][0], z1 = d.z[0][1];
+  const double a1 = s_a[0], a2 = s_a[1];
+  const bool first = (d.flags & kFirst) != 0;
+  double bestd = INFINITY;
+  int bestk = INT_MAX;
+  for (unsigned k = tid; k < s; k += blockDim.x) {
+    const int j = 3 + 2 * static_cast<int>(k);
+    double P[5][5];
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) P[a][b] = s_P33[a][b];
+    const double r0j0 = static_cast<double>(S[j]), r0j1 = static_cast<double>(S[j + 1]);
+    for (int a = 0; a < 3; ++a) {
+      const double aa = first ? alpha_of(a, a1, a2) : 0.0;
+      P[a][3] = static_cast<double>(S[a * ld + j]) + aa * r0j0;
+      P[a][4] = static_cast<double>(S[a * ld + j + 1]) + aa * r0j1;
+    }
+    for (int e = 0; e < 2; ++e) {
+      const T* row = S + static_cast<size_t>(j + e) * ld;
+      const double rj0 = static_cast<double>(row[0]);
+      for (int b = 0; b < 3; ++b) {
+        const double ab = first ? alpha_of(b, a1, a2) : 0.0;
+        P[3 + e][b] = static_cast<double>(row[b]) + rj0 * ab;
+      }
+      P[3 + e][3] = static_cast<double>(row[j]);
+      P[3 + e][4] = static_cast<double>(row[j + 1]);
+    }
+    const double dist = assoc_dist(P, s_pose, x[j], x[j + 1], z0, z1, A.r);
+    if (dist < bestd) {  // strict: first index kept, NaN never selected
+      bestd = dist;
+      bestk = static_cast<int>(k);
+    }
+  }
+  wave_argmin(bestd, bestk);  // 64 lanes, ties → lower index (DPP, ekf_math.hpp)
+  const int wv = tid >> 6;
+  if ((tid & 63) == 0) {
+    s_bd[wv] = bestd;
+    s_bk[wv] = bestk;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < static_cast<int>(blockDim.x >> 6); ++w)
+      if (s_bd[w] < bestd || (s_bd[w] == bestd && s_bk[w] < bestk)) {
+        bestd = s_bd[w];
+        bestk = s_bk[w];
+      }
+    // the new slot (index s, d = gate) wins only over a strictly larger existing minimum
+    if (!(bestd <= A.gate)) {
+      const int js = 3 + 2 * static_cast<int>(s);
+      x[js] = s_pose[1] + z0 * cos(z1 + s_pose[0]);      // slam.cpp:351-354
+      x[js + 1] = s_pose[2] + z0 * sin(z1 + s_pose[0]);
+      ctl->counter = s + 1;
+      ctl->assoc_j[slot] = static_cast<int>(s);
+      ctl->assoc_new[slot] = 1;
+    } else {
+      ctl->assoc_j[slot] = bestk;
+      ctl->assoc_new[slot] = 0;
+    }
+  }
+}
+
+template <typename T>
+hipError_t launch_assoc(const PassArgs<T>& a, int nf, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+  launch(k_assoc<T>, dim3(1, nf), dim3(kAssocThreads), s, e0, e1, a);
+  return hipGetLastError();
+}
+template hipError_t launch_assoc<double>(const PassArgs<double>&, int, hipStream_t, hipEvent_t,
+                                         hipEvent_t);
+template hipError_t launch_assoc<float>(const PassArgs<float>&, int, hipStream_t, hipEvent_t,
+                                        hipEvent_t);
 
 }  // namespace ekfslam

@@ -1,28 +1,28 @@
-// HIP kernels (gfx950 / CDNA4) for the EKF-SLAM predict → correct* → posterior path of
-// maxipalay/ekf-slam nuslam/src/slam.cpp.
+// k_chain (gfx950 / CDNA4): the sequential part of the EKF-SLAM predict → correct* → posterior path
+// of maxipalay/ekf-slam nuslam/src/slam.cpp.
 //
 // A chunk (one message, up to kMaxChunk markers) runs as three kernels:
 //
-//   k_chain       One workgroup per filter. The m corrections of a chunk only couple through the
-//                 rows/columns the chunk touches, U = {θ, x, y} ∪ {jx, jy per marker} (|U| ≤ 3+2m).
-//                 The chain replays them on the |U|×|U| block in LDS (predict folded in) — the only
-//                 sequential part — and hands the factor kernel the row / column maps Z (|U|×2m) and
-//                 Y (2m×|U|) plus x[U] through a write-through record (ChunkRec).
-//   k_factors     Kcat = Σ_pred[:, U]·Z and Mcat = Y·Σ_pred[U, :] for every row / column on f64
-//                 MFMA (v_mfma_f64_16x16x4f64), plus the new state x.
-//   k_sigma_pass  Σ_out = Σ_in + Q̄ − Σ_k Kcat[k]ᵀ ⊗ Mcat[k], a rank-(2+2m) update of the dense
-//                 covariance: the predict's two rank-1 terms (A Σ Aᵀ, slam.cpp:198) and one rank-2
-//                 term per correction ((I − KH)Σ, slam.cpp:264-265). It streams Σ once per chunk
-//                 through MFMA (v_mfma_f32_32x32x2f32 for fp32 Σ, v_mfma_f64_16x16x4f64 for fp64),
-//                 so the HBM cost of a correction is 2·n²·w / m instead of 2·n²·w.
+//   k_chain       (this file) One workgroup per filter. The m corrections of a chunk only couple
+//                 through the rows/columns the chunk touches, U = {θ, x, y} ∪ {jx, jy per marker}
+//                 (|U| ≤ 3+2m). The chain replays them on the |U|×|U| block in LDS (predict folded
+//                 in) — the only sequential part — and hands the factor kernel the row / column
+//                 maps Z (|U|×2m) and Y (2m×|U|) plus x[U] through a write-through record (ChunkRec).
+//   k_factors     (ekf_factors.hip) Kcat = Σ_pred[:, U]·Z and Mcat = Y·Σ_pred[U, :] for every row /
+//                 column on f64 MFMA (v_mfma_f64_16x16x4f64), plus the new state x.
+//   k_sigma_pass  (ekf_sigma_pass.hip) Σ_out = Σ_in + Q̄ − Σ_k Kcat[k]ᵀ ⊗ Mcat[k], a rank-(2+2m)
+//                 update of the dense covariance: the predict's two rank-1 terms (A Σ Aᵀ,
+//                 slam.cpp:198) and one rank-2 term per correction ((I − KH)Σ, slam.cpp:264-265). It
+//                 streams Σ once per chunk through MFMA (v_mfma_f32_32x32x2f32 for fp32 Σ,
+//                 v_mfma_f64_16x16x4f64 for fp64), so the HBM cost of a correction is 2·n²·w / m
+//                 instead of 2·n²·w.
 //
 // Equal to the reference's sequential dense algebra in exact arithmetic; the summation order
-// differs (tolerances in tests/). Unknown association adds k_assoc before each single-marker chunk.
+// differs (tolerances in tests/). Unknown association adds k_assoc (ekf_assoc.hip) before each
+// single-marker chunk.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
-#include <climits>
 #include <cstdint>
 #include <type_traits>
 
@@ -33,101 +33,25 @@
 
 namespace ekfslam {
 
-// Diagnostic build only (tools/chain_stamps.py): s_memtime stamps of k_chain's block (0,0), thread
-// 0, in a ring of the last four chunks (by seq & 3).
+#include "ekf_diag.hpp"  // (EKF_STAMP*, EKF_DUMP_BLOCK; empty in the product library)
 #ifdef EKF_DIAG_STAMPS
 __device__ unsigned long long g_stamps[4 * 512];
-#define EKF_STAMP(i)                                                              \
-  do {                                                                            \
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)                   \
-      g_stamps[512 * (seq & 3) + (i)] = __builtin_amdgcn_s_memtime();             \
-  } while (0)
-#define EKF_STAMPT(i, t)                                                          \
-  do {                                                                            \
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == (t))                 \
-      g_stamps[512 * (seq & 3) + (i)] = __builtin_amdgcn_s_memtime();             \
-  } while (0)
-#define EKF_STAMPV(i, v)                                                          \
-  do {                                                                            \
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)                   \
-      g_stamps[512 * (seq & 3) + (i)] = (v);                                      \
-  } while (0)
-#else
-#define EKF_STAMPT(i, t) \
-  do {                   \
-  } while (0)
-#define EKF_STAMPV(i, v) \
-  do {                   \
-  } while (0)
-#define EKF_STAMP(i) \
-  do {               \
-  } while (0)
-#endif
-#ifdef EKF_DIAG_STAMPS
+__device__ double g_blocks[64][kMaxU][kMaxU + 1];
+__device__ double g_blockx[64][kMaxU];
 }  // namespace ekfslam
 extern "C" int ekfslam_diag_read_stamps(unsigned long long* out, int n) {
   using ekfslam::g_stamps;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * (n < 2048 ? n : 2048)) == hipSuccess ? 0 : -5;
 }
-namespace ekfslam {
-#endif
-
-// Diagnostic build only (tools/diag_blocks.py): filter 0's chain block Σ[U, U] and x[U] as the
-// corrections start (predict folded in), per chunk sequence number mod 64.
-#ifdef EKF_DIAG_STAMPS
-__device__ double g_blocks[64][kMaxU][kMaxU + 1];
-__device__ double g_blockx[64][kMaxU];
-}  // namespace ekfslam
 extern "C" int ekfslam_diag_read_blocks(double* blocks, double* xs) {
   using namespace ekfslam;
   if (hipMemcpyFromSymbol(blocks, HIP_SYMBOL(g_blocks), sizeof(g_blocks)) != hipSuccess) return -5;
   return hipMemcpyFromSymbol(xs, HIP_SYMBOL(g_blockx), sizeof(g_blockx)) == hipSuccess ? 0 : -5;
 }
 namespace ekfslam {
-#define EKF_DUMP_BLOCK(seq)                                                         \
-  do {                                                                              \
-    __syncthreads();                                                                \
-    if (blockIdx.y == 0) {                                                          \
-      for (int e = threadIdx.x; e < kMaxU * (kMaxU + 1); e += blockDim.x)           \
-        (&g_blocks[(seq) & 63][0][0])[e] = (&P[0][0])[e];                             \
-      if (threadIdx.x < kMaxU) g_blockx[(seq) & 63][threadIdx.x] = sh.xU[0][threadIdx.x]; \
-    }                                                                               \
-    __syncthreads();                                                                \
-  } while (0)
-#else
-#define EKF_DUMP_BLOCK(seq) \
-  do {                      \
-  } while (0)
 #endif
 
-
-// Diagnostic build only (tools/sigma_bench.hip): s_memrealtime (100 MHz) per Σ-pass workgroup.
-#ifdef EKF_DIAG_STAMPS
-__device__ unsigned long long g_sig_stamps[4096][5];
-#define SIG_STAMP(i)                                                                   \
-  do {                                                                                 \
-    if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096) {                    \
-      g_sig_stamps[blockIdx.x][i] = __builtin_amdgcn_s_memrealtime();                  \
-      if (i == 0)                                                                      \
-        g_sig_stamps[blockIdx.x][4] =                                                  \
-            (static_cast<unsigned long long>(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (15 << 11))) << 32) | \
-            __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));                \
-    }                                                                                  \
-  } while (0)
-#else
-#define SIG_STAMP(i) \
-  do {               \
-  } while (0)
-#endif
-
-// f64 MFMA 16×16×4: A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15],
-// D[row = (lane>>4) + 4r][col = lane&15] (the f64 C/D map differs from the f32 one).
-typedef double d4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-
+#include "ekf_sync.hpp"  // (hand-off protocol, lds_barrier and buffer-descriptor helpers)
 
 // J: the Joseph-form instantiation (round 6: a whole message of ≤ 16 markers per chunk): its row
 // maps Z hold Zv beside Z (4m ≤ 64 columns) and V, S, C', D' are kept per step; the simple form's
@@ -191,17 +115,6 @@ struct ChainSharedT {
   int zdone;     // Joseph: steps whose Z_c, Zv_c wave 1 has stored (wave 2 reads them)
 };
 
-
-#include "ekf_sync.hpp"  // (hand-off protocol and buffer-descriptor helpers)
-
-// A workgroup barrier that orders LDS only: global loads in flight stay in flight across it
-// (__syncthreads waits vmcnt(0), and vmcnt counts loads too).
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // Intra-workgroup hand-off through LDS (waves on different SIMDs; no s_barrier).
 // The LDS executes one wave's accesses in issue order, so a flag stored after the data is seen
 // after it by any wave: no s_waitcnt before the flag (a release would drain every LDS op of the
@@ -237,39 +150,9 @@ __device__ __forceinline__ void lds_wait_ge3(const __attribute__((address_space(
 // J: a Joseph chunk (m ≤ kMaxJoseph). Every step then also subtracts V_c·K_cᵀ, V_c = Σ_c·Hᵀ − K_c·S_c
 // (slam.cpp:264-265's update as (I − KH)Σ(I − KH)ᵀ + K·R·Kᵀ expanded), always after the K_c·M_c term
 // — the order wave 3 uses, so an entry both waves compute has the same bits.
-// The diagnostic build (EKF_DIAG_STAMPS, libekfslam_diag.so) also carries the hand-off
-// instrumentation behind PassArgs::dbg (EKF_DBG_ORDER, tools/diag_handover.py, tools/diag_dlog.py);
-// in the product library every such branch folds away.
-#ifdef EKF_DIAG_STAMPS
-constexpr bool kDiagBuild = true;
-#else
-constexpr bool kDiagBuild = false;
-#endif
-
-// dev only (PassArgs::dbg & 16): order-independent wrapping sums of the bit patterns a kernel read
-// or wrote, A.dlog[kind][seq % 64][f % 64][slot]
-__device__ __forceinline__ unsigned long long dbits(double v) {
-  return static_cast<unsigned long long>(__double_as_longlong(v));
-}
-__device__ __forceinline__ unsigned long long dbits(float v) { return __float_as_uint(v); }
-template <typename T>
-__device__ __forceinline__ void dlog_add(const PassArgs<T>& A, int kind, unsigned seq, int f,
-                                         int slot, unsigned long long v) {
-  atomicAdd(A.dlog + ((static_cast<size_t>(kind) * 64 + (seq & 63u)) * 64 + (f & 63)) * 8 + slot, v);
-}
-
-// dev only (PassArgs::dbg & 16): step c's wrapping sums at lg[(kChainLogKind + c)·64·64·8 + slot]
-constexpr int kChainLogKind = 5;
-__device__ __forceinline__ unsigned long long dbits0(double v) {
-  return static_cast<unsigned long long>(__double_as_longlong(v));
-}
-__device__ __forceinline__ void steplog(unsigned long long* lg, int c, int slot, unsigned long long v) {
-  atomicAdd(lg + static_cast<size_t>(kChainLogKind + c) * 64 * 64 * 8 + slot, v);
-}
-
 template <bool J>
 __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, int m, int nu,
-                                         double r_noise, unsigned seq, unsigned long long* lg) {
+                                         double r_noise, unsigned seq) {
   LdsChain<J>& sh = *shp;
   constexpr int JM = ChainSharedT<J>::JM;
   LdsDesc& d = *dp;
@@ -398,15 +281,6 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
         }
       }
     }
-    if (kDiagBuild && lg) {
-      if (lane == 0) {
-        steplog(lg, c, 0, dbits0(Sm_keep[0]) + dbits0(Sm_keep[1]) + dbits0(Sm_keep[2]) +
-                              dbits0(Sm_keep[3]) + dbits0(Si[0]) + dbits0(Si[3]));
-        steplog(lg, c, 1, dbits0(nv0) + dbits0(nv1) + dbits0(zhat[0]) + dbits0(zhat[1]) +
-                              dbits0(H0[1]) + dbits0(H1[2]));
-      }
-      if (lane < nu) steplog(lg, c, 2, dbits0(ka) + dbits0(kb) + dbits0(mm0) + dbits0(mm1));
-    }
     // The next marker's cross operands (Bx = {0, 1, 2, nx, nx+1}) after step c−1. Pose columns /
     // rows: pk / pm (pA ⊃ pose). The nx columns / rows were read one step back (rn / qn, after
     // step c−2) and get step c−1's rank-2 term here from registers: K_{c−1} of this lane (kp)
@@ -460,12 +334,6 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
         qn[j] = sh.P[pb][nx + 2 + j][lr];
       }
     }
-    if (kDiagBuild && lg && lane < nu) {
-      unsigned long long v = 0;
-      for (int k = 0; k < 5; ++k) v += dbits0(xr[k]) + dbits0(xq[k]);
-      steplog(lg, c, 3, v);
-      steplog(lg, c, 7, dbits0(rn[0]) + dbits0(rn[1]) + dbits0(qn[0]) + dbits0(qn[1]));
-    }
     const int jx = __builtin_amdgcn_readlane(ul, pj);  // sh.u[pj] (ul = sh.u[lane], pj < kMaxU)
     EKF_STAMP(67 + 8 * c);
     const double K0 = ka * Si[0] + kb * Si[2];  // K = Σ·Hᵀ·S⁻¹
@@ -487,10 +355,6 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
       }
       xl = xt;
       *(lane < nu ? &sh.xU[0][lane] : &sh.junk[0][lane]) = xt;
-      if (kDiagBuild && lg && lane < nu) {
-        steplog(lg, c, 4, dbits0(K0) + dbits0(K1));
-        steplog(lg, c, 5, dbits0(xt));
-      }
     }
     {
       const bool in = lane < nu, st = lane < kMaxU;
@@ -565,11 +429,6 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
         pm[k] = v;
         *(later ? &sh.P[pb][row][lane] : &sh.junk[0][lane]) = v;
       }
-      if (kDiagBuild && lg && lane < nu) {
-        unsigned long long v = 0;
-        for (int k = 0; k < 5; ++k) v += dbits0(pk[k]) + dbits0(pm[k]);
-        steplog(lg, c, 6, v);
-      }
       // (the Bx × Bx entries: lane `row` stored the same value as its pk, same operands)
       kp0 = K0;
       kp1 = K1;
@@ -581,7 +440,6 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
     EKF_STAMP(70 + 8 * c);
   }
 }
-
 
 // The previous chunk's predict on the gathered rebuild operands: v + α_i·Σ[0][j] +
 // (Σ[i][0] + α_i·Σ00)·α_j + Q̄, for D = Σ_in'[U, U] → P, R = Σ_in'[U, U'] → pv.R and
@@ -688,248 +546,6 @@ __device__ __forceinline__ void rebuild_rcd(Shared& sh, double (&P)[kMaxU][kMaxU
   }
 }
 
-template <bool J>
-struct FactorSharedT {
-  static constexpr int ZC = J ? kZJ : kZC;  // the record's Z columns in use (Joseph: Z and Zv)
-  int u[kMaxU + 1];
-  double alphaU[kMaxU], row0raw[kMaxU], col0raw[kMaxU], Zx[kMaxU], xU[kMaxU];
-  double Z[kMaxU][ZC + 1];
-  double Y[kZC][kMaxU + 1];
-  double a1, a2, s00;
-  int nu;
-};
-
-// The factor kernel's two halves: a chunk's record into LDS, then one wave's 16 indices of Kcat = R_pred·Z (rows) and
-// Mcat = Y·C_pred (columns) on f64 MFMA, plus the new state.
-// R_pred(i)[b] = Σ_pred[i][u_b], C_pred(j)[a] = Σ_pred[u_a][j].
-template <bool J>
-__device__ __forceinline__ void factor_record(const ChunkRec* rec, FactorSharedT<J>& sh, int tid) {
-  constexpr int ZC = FactorSharedT<J>::ZC;
-  {  // the record into LDS: every load of a thread issued before its first LDS store
-    constexpr int kPer = (kMaxU * kZC + 255) / 256;  // 5
-    constexpr int kPerZ = (kMaxU * ZC + 255) / 256;  // 5 (Joseph: 9)
-    double vz[kPerZ], vy[kPer];
-#pragma unroll
-    for (int i = 0; i < kPerZ; ++i) {  // (the record's rows are kZJ wide)
-      const int e = min(tid + 256 * i, kMaxU * ZC - 1);
-      vz[i] = rec->Z[e / ZC][e % ZC];
-    }
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = min(tid + 256 * i, kMaxU * kZC - 1);
-      vy[i] = (&rec->Y[0][0])[e];
-    }
-#pragma unroll
-    for (int i = 0; i < kPerZ; ++i) {
-      const int e = tid + 256 * i;
-      if (e < kMaxU * ZC) {
-        const int b = e / ZC, k = e - b * ZC;
-        sh.Z[b][k] = vz[i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = tid + 256 * i;
-      if (e < kMaxU * kZC) {
-        const int k2 = e / kMaxU, b2 = e - k2 * kMaxU;
-        sh.Y[k2][b2] = vy[i];
-      }
-    }
-  }
-  if (tid < kMaxU) {
-    sh.u[tid] = rec->u[tid];
-    sh.alphaU[tid] = rec->alphaU[tid];
-    sh.row0raw[tid] = rec->row0raw[tid];
-    sh.col0raw[tid] = rec->col0raw[tid];
-    sh.Zx[tid] = rec->Zx[tid];
-    sh.xU[tid] = rec->xU[tid];
-  }
-  if (tid == 0) {
-    sh.a1 = rec->a1;
-    sh.a2 = rec->a2;
-    sh.s00 = rec->s00;
-    sh.nu = rec->nu;
-  }
-}
-
-template <typename T, bool J>
-__device__ __forceinline__ void factor_wave(const PassArgs<T>& A, const MsgDesc& d, int f, int wg,
-                                            const FactorSharedT<J>& sh, int lane) {
-  constexpr int NG = FactorSharedT<J>::ZC / 16;  // 16-column groups of Z: 2 (Joseph: 4)
-  const int n = A.n, ld = A.ld, ldk = A.ldk;
-  const T* S = A.sig[d.parity] + f * A.sig_stride;
-  const double* xin = A.x[d.parity] + f * A.x_stride;
-  double* xout = A.x[d.parity ^ 1] + f * A.x_stride;
-  T* kc = A.kcat + f * A.km_stride;
-  T* mc = A.mcat + f * A.km_stride;
-  const bool first = (d.flags & kFirst) != 0;
-  const bool joseph = J && (d.flags & kJoseph) != 0;
-  // Joseph: Mcat rows 2 + 2m .. 2 + 4m − 1 hold K_c (the V_c·K_cᵀ term's column factor), written
-  // by the row waves; the column waves leave them alone
-  const int jk0 = joseph ? 2 * d.m : kZC, jk1 = joseph ? 4 * d.m : kZC;
-  const int nu = sh.nu;
-  const double* xfin = sh.xU;
-  // ---- phase B: Kcat = R_pred·Z, Mcat = Y·C_pred on f64 MFMA, 16 rows (or columns) per wave ----
-  // R_pred(i)[b] = Σ_pred[i][u_b], C_pred(j)[a] = Σ_pred[u_a][j] (predict folded in as above).
-  const int row_tiles = (n + 15) / 16;
-  const int ks = lane >> 4, l16 = lane & 15;
-  const double s00 = sh.s00;
-  // Mcat columns j = C0 + l16 of a wave from Σ_in[U, j] (raw) and Σ_in[0, j] (c0t)
-  auto columns = [&](int j, const T (&raw)[9], T c0t) {
-    const bool vj = j < n;
-    const double c0raw = vj ? static_cast<double>(c0t) : 0.0;
-    const double aj = first ? alpha_of(j, sh.a1, sh.a2) : 0.0;
-    double bv[9];
-#pragma unroll
-    for (int s = 0; s < 9; ++s) {
-      const int k = 4 * s + ks;
-      double v = (vj && k < nu) ? static_cast<double>(raw[s]) : 0.0;
-      if (first && vj && k < nu) {
-        v = v + sh.alphaU[k] * c0raw;
-        v = v + (sh.col0raw[k] + sh.alphaU[k] * s00) * aj;
-        if (sh.u[k] == j && j < 3) v += A.q;
-      }
-      bv[s] = v;
-    }
-    d4 acc0 = {0, 0, 0, 0}, acc1 = {0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < 9; ++s) {
-      const int k = 4 * s + ks;
-      const double y0 = k < kMaxU ? sh.Y[l16][k] : 0.0;
-      const double y1 = k < kMaxU ? sh.Y[16 + l16][k] : 0.0;
-      acc0 = mfma_f64(y0, bv[s], acc0);
-      acc1 = mfma_f64(y1, bv[s], acc1);
-    }
-    if (vj && ks == 0) {
-      mc[0 * ldk + j] = static_cast<T>(first ? c0raw : 0.0);
-      mc[1 * ldk + j] = static_cast<T>(first ? aj : 0.0);
-    }
-    if (vj) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int kr = ks + 4 * r;
-        if (kr < jk0 || kr >= jk1) mc[(2 + kr) * ldk + j] = static_cast<T>(acc0[r]);
-        if (16 + kr < jk0 || 16 + kr >= jk1) mc[(18 + kr) * ldk + j] = static_cast<T>(acc1[r]);
-      }
-    }
-  };
-  // fp64: Σ_in is symmetric, so a row wave's Σ_in[U, i] are also its columns' — one wave per 16
-  // indices builds both Kcat rows and Mcat columns (half the waves and half the Σ_in reads of
-  // separate row and column waves, the same values)
-  constexpr bool merged = sizeof(T) == 8;
-  if (wg < row_tiles) {
-    const int R0 = wg * 16;
-    const int i = R0 + l16;
-    const bool vi = i < n;
-    const T* rowp = S + static_cast<size_t>(vi ? i : 0) * ld;
-    // every gather issued unconditionally (clamped index; padding u = 0 stays in bounds), then
-    // masked: a predicated load would be a branch with its own wait, one round trip per load
-    T raw[9];
-    T r0t;
-    if (sizeof(T) == 8) {
-      // fp64 Σ is symmetric (the symmetric Σ pass mirrors every element below the diagonal), so
-      // Σ_in[i, U] is read as Σ_in[U, i]: 16 consecutive i per row of U (128 B) instead of one
-      // scattered element per lane and column of U
-      r0t = S[vi ? i : 0];
-#pragma unroll
-      for (int s = 0; s < 9; ++s)
-        raw[s] = S[static_cast<size_t>(sh.u[min(4 * s + ks, kMaxU - 1)]) * ld + (vi ? i : 0)];
-    } else {
-      r0t = rowp[0];
-#pragma unroll
-      for (int s = 0; s < 9; ++s) raw[s] = rowp[sh.u[min(4 * s + ks, kMaxU - 1)]];
-    }
-    const double r0raw = vi ? static_cast<double>(r0t) : 0.0;
-    const double ai = first ? alpha_of(i, sh.a1, sh.a2) : 0.0;
-    double av[9];
-#pragma unroll
-    for (int s = 0; s < 9; ++s) {
-      const int k = 4 * s + ks;
-      double v = (vi && k < nu) ? static_cast<double>(raw[s]) : 0.0;
-      if (first && vi && k < nu) {
-        v = v + ai * sh.row0raw[k];
-        v = v + (r0raw + ai * s00) * sh.alphaU[k];
-        if (i == sh.u[k] && i < 3) v += A.q;
-      }
-      av[s] = v;
-    }
-    d4 acc[NG], acc2 = {0, 0, 0, 0};
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g] = d4{0, 0, 0, 0};
-#pragma unroll
-    for (int s = 0; s < 9; ++s) {
-      const int k = 4 * s + ks;
-      const double zx = (k < kMaxU && l16 == 0) ? sh.Zx[k] : 0.0;
-      // Zᵀ·R rather than R·Z: the lane then holds Kcat[c = ks + 4r][i = R0 + l16], so each store
-      // covers 4 factor rows × 128 B instead of 16 rows × 32 B (the same products and sums)
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-        acc[g] = mfma_f64(k < kMaxU ? sh.Z[k][16 * g + l16] : 0.0, av[s], acc[g]);
-      acc2 = mfma_f64(zx, av[s], acc2);
-    }
-    if (kDiagBuild && (A.dbg & 16)) {  // Σ_in as read, x_in as read
-      unsigned long long s2 = 0;
-#pragma unroll
-      for (int s = 0; s < 9; ++s) s2 += dbits(raw[s]);
-      s2 += dbits(r0t);
-      dlog_add(A, 4, A.seq, f, 2, s2);
-    }
-    if (vi && ks == 0) {  // the predict's two rank-1 factors (slam.cpp:198)
-      kc[0 * ldk + i] = static_cast<T>(first ? -ai : 0.0);
-      kc[1 * ldk + i] = static_cast<T>(first ? -(r0raw + ai * s00) : 0.0);
-      // rows of U take the chain's x (first position of the row in U)
-      int pos = kMaxU;
-#pragma unroll
-      for (int k = kMaxU - 1; k >= 0; --k) pos = (k < nu && sh.u[k] == i) ? k : pos;
-      xout[i] = pos < nu ? xfin[pos] : xin[i] + acc2[0];
-      if (kDiagBuild && (A.dbg & 16)) {
-        dlog_add(A, 4, A.seq, f, 3, dbits(xin[i]));
-        dlog_add(A, 4, A.seq, f, 4, dbits(pos < nu ? xfin[pos] : xin[i] + acc2[0]));
-      }
-    }
-    if (vi) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = 16 * g + ks + 4 * r;
-          // Joseph: Z columns 0 .. 2m − 1 (the first two groups) are K, which is also the column
-          // factor of the (ΣHᵀ − K·S)·Kᵀ term (Mcat rows 2 + 2m + c); columns 32 + c are V, Kcat
-          // rows 2 + 2m + c — the rank-(2 + 4m) factors packed, zero columns not stored
-          if (!joseph) {
-            if (g < 2) kc[(2 + c) * ldk + i] = static_cast<T>(acc[g][r]);
-          } else if (g < 2) {
-            if (c < jk0) {
-              kc[(2 + c) * ldk + i] = static_cast<T>(acc[g][r]);
-              mc[(2 + jk0 + c) * ldk + i] = static_cast<T>(acc[g][r]);
-            }
-          } else if (c - kZC < jk0 + 2) {  // (+ the two zero rows up to kw = 4m + 4: the
-            // pass reads them, and a longer chunk before may have left V rows there)
-            kc[(2 + jk0 + c - kZC) * ldk + i] = static_cast<T>(acc[g][r]);
-          }
-        }
-    }
-    if (merged) columns(i, raw, r0t);
-  } else if (!merged && wg < 2 * row_tiles) {
-    const int C0 = (wg - row_tiles) * 16;
-    const int j = C0 + l16;
-    const bool vj = j < n;
-    const int jj = vj ? j : 0;
-    T raw[9];
-    const T c0t = S[jj];
-#pragma unroll
-    for (int s = 0; s < 9; ++s)
-      raw[s] = S[static_cast<size_t>(sh.u[min(4 * s + ks, kMaxU - 1)]) * ld + jj];
-    columns(j, raw, c0t);
-  }
-}
-
-// 16 rows or 16 columns per wave (fp64: both), per_filter workgroups of 4 waves per filter
-template <typename T>
-__host__ __device__ inline int factor_waves(const PassArgs<T>& a) {
-  return (sizeof(T) == 8 ? 1 : 2) * ((a.n + 15) / 16);
-}
-
 // One workgroup per filter, persistent over the `nchunks` chunks of a launch (descriptors
 // A.desc[i·desc_stride + filter]): per chunk the m sequential corrections on the |U|×|U| block.
 // Every chunk of a launch after the first rebuilds its block from the chunk before (kLook): the
@@ -937,16 +553,6 @@ __host__ __device__ inline int factor_waves(const PassArgs<T>& a) {
 // chain's own final block into the next chunk instead was 6 % faster but let the chain's block and
 // the HBM Σ drift apart — two roundings of the 1e7-prior first sightings — until a survey replay
 // went non-finite; the rebuild keeps every schedule bit-identical)
-// dev only (PassArgs::dbg & 8): kernel `k` (0 chain, 1 factors, 2 Σ pass) of filter f runs with
-// launch epoch e; the launches of a kind are stream-ordered, so e must exceed the last one seen
-// (a kernel that runs with an older launch's arguments counts at sync[kSyncDbg + 3 + k])
-template <typename T>
-__device__ void dbg_seq_check(const PassArgs<T>& A, int k, int f, unsigned e) {
-  unsigned* last = A.sync + kSyncChain + (1 + k) * A.rec_stride + f;
-  if (static_cast<int>(e - *last) <= 0) atomicAdd(A.sync + kSyncDbg + 3 + k, 1u);
-  *last = e;
-}
-
 template <typename T, bool J>
 __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchunks) {
   __shared__ ChainSharedT<J> sh;
@@ -971,7 +577,6 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
   // kernels (two streams without CU masks: > 32 filters with EKF_SERIAL=0), DESIGN.md §5.
   __syncthreads();
   if (tid == 0) sh.npose_ci = -1;  // (ordered before its first reader by the chunk loop's barriers)
-  if (kDiagBuild && (A.dbg & 1)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   bool pre = false;        // sdesc[ci & 1] was prefetched by the previous chunk's epilogue
   unsigned pending = 0;    // chain epoch of the previous chunk, not yet published (its record
                            // stores are still in flight; see the epilogue)
@@ -1002,15 +607,10 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
   }
   if (!active) continue;  // this filter sits the chunk out
   const unsigned seq = A.seq + static_cast<unsigned>(ci);
-  if ((kDiagBuild && (A.dbg & 8)) && tid == 0) dbg_seq_check(A, 0, f, seq + 1u);
   // Σ_in / x / records a rebuilding chain reads come from the Σ pass two launches back (bulk
   // stream), and this record parity is free again once that pass is done (its factor kernel read
   // it); a chunk that gathers its own Σ_in needs the pass one back.
   const unsigned need = look ? (seq >= 2 ? seq - 1 : 0u) : seq;
-  if ((kDiagBuild && (A.dbg & 4)) && need && tid == 0) {
-    if (static_cast<int>(epoch_load(A.sync + kSyncSigma) - need) < 0) atomicAdd(A.sync + kSyncDbg, 1u);
-    atomicAdd(A.sync + kSyncDbg + 2, 1u);
-  }
   // A0's associated ids (k_assoc, earlier on this stream), loaded unconditionally (clamped) and
   // here, so that the barrier below completes them: under A0's branch the load was waited for,
   // vmcnt(0), together with every early load below
@@ -1037,8 +637,6 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
   // V_c = G_c − K_c·S_c beside K_c, column factor K_cᵀ beside M_c: the record's Z carries V_c's
   // row map in columns 32 + 2c.. (kZC + 2c), the chain's block gets the term step by step.
   const bool joseph = J && (d.flags & kJoseph) != 0;
-  if ((kDiagBuild && (A.dbg & 16)) && tid < static_cast<int>(sizeof(MsgDesc) / 8))
-    dlog_add(A, 0, seq, f, 0, reinterpret_cast<const unsigned long long*>(&d)[tid]);
 
   // kLook: this chunk's Σ_in is still being written by the previous chunk's Σ pass. Rebuild what
   // the chain needs from the chunk before: Σ_in' (the other buffer, complete) and its record.
@@ -1173,25 +771,6 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
       pa1 = rp->a1;
       pa2 = rp->a2;
       tq = ctl->tmo[tid < 3 ? tid : 0];
-    }
-    if (kDiagBuild && (A.dbg & 16)) {
-      unsigned long long s2 = 0, s4 = 0;
-#pragma unroll
-      for (int i = 0; i < kPer; ++i) {
-        s2 += dbits(vd[i]) + dbits(vr[i]) + dbits(vc[i]);
-        s4 += dbits(vy[i]);
-      }
-#pragma unroll
-      for (int i = 0; i < kPerZ; ++i) s4 += dbits(vz[i]);
-      if (tid < kMaxU) {
-        s2 += dbits(r0u) + dbits(c0u) + dbits(r0p) + dbits(c0p);
-        s4 += dbits(x0) + dbits(x1);
-        dlog_add(A, 0, seq, f, 3, dbits(x2));
-      }
-      if (tid == 0) s4 += static_cast<unsigned>(pflags) + dbits(pa1) + dbits(pa2);
-      if (tid < 3) dlog_add(A, 0, seq, f, 1, dbits(tq));
-      dlog_add(A, 0, seq, f, 2, s2);
-      dlog_add(A, 0, seq, f, 4, s4);
     }
 #pragma unroll
     for (int i = 0; i < kPerZ; ++i) {
@@ -1501,14 +1080,6 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     const double xv = xin[sh.u[tid < nu ? tid : 0]];
     const double xq = xin[tid < 3 ? tid : 0];
     const double tq = ctl->tmo[tid < 3 ? tid : 0];
-    if (kDiagBuild && (A.dbg & 16)) {
-      unsigned long long s2 = 0;
-#pragma unroll
-      for (int i = 0; i < kPer; ++i) s2 += dbits(vd[i]);
-      dlog_add(A, 0, seq, f, 2, s2);
-      dlog_add(A, 0, seq, f, 3, dbits(xv) + dbits(xq));
-      if (tid < 3) dlog_add(A, 0, seq, f, 1, dbits(tq));
-    }
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       const int e = tid + i * kChainThreads;
@@ -1588,9 +1159,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
   }
   EKF_STAMP(19);
   if (wave == 0) {
-    unsigned long long* lg =
-        (kDiagBuild && (A.dbg & 16)) ? A.dlog + (static_cast<size_t>(seq & 63u) * 64 + (f & 63)) * 8 : nullptr;
-    chain_wave0<J>((LdsChain<J>*)(&sh), (LdsDesc*)(&d), 0, m, nu, A.r, seq, lg);
+    chain_wave0<J>((LdsChain<J>*)(&sh), (LdsDesc*)(&d), 0, m, nu, A.r, seq);
   } else if (wave == 3) {  // P outside the cross: rows and columns ∉ the next marker's Bx
     // lane → column 3+(lane&31), rows 3.. of parity lane>>5. The lane's 16 entries stay in
     // registers for the whole chunk: every step's rank-2 term is applied to all of them — also to
@@ -1649,9 +1218,6 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
       ctl->tmo[0] = tmo.theta;
       ctl->tmo[1] = tmo.x;
       ctl->tmo[2] = tmo.y;
-      if (kDiagBuild && (A.dbg & 16))
-        dlog_add(A, 0, A.seq + static_cast<unsigned>(ci), f, 6,
-                 dbits(tmo.theta) + dbits(tmo.x) + dbits(tmo.y));
       sh.tmo[0] = tmo.theta;
       sh.tmo[1] = tmo.x;
       sh.tmo[2] = tmo.y;
@@ -2105,7 +1671,6 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
       const double zx = sh.Zx[tid];  // (wave 1's sum over the corrections)
       const bool in = tid < nu;
       st_wt(&rec->Zx[tid], zx);
-      if (kDiagBuild && (A.dbg & 16)) dlog_add(A, 0, seq, f, 5, dbits(zx) + dbits(in ? xfin[tid] : 0.0));
       st_wt(&rec->u[tid], sh.u[tid]);
       st_wt(&rec->alphaU[tid], in ? sh.alphaU[tid] : 0.0);
       st_wt(&rec->row0raw[tid], in ? sh.row0raw[tid] : 0.0);
@@ -2133,841 +1698,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     __syncthreads();
     if (tid == 0) epoch_store(A.sync + kSyncChain + f, pending);
   }
-  if (kDiagBuild && (A.dbg & 2)) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 }
-
-template <typename T, bool J>
-__global__ __launch_bounds__(256) void k_factors(PassArgs<T> A, int xcd_b, int nf) {
-  __shared__ FactorSharedT<J> sh;
-  constexpr int ZC = FactorSharedT<J>::ZC;
-  // xcd_b = 0: grid (blocks per filter, filters). xcd_b = B > 0 (swarms): the Σ pass's XCD-aware
-  // 1-D grid — block L on XCD L % 8 takes filter 8·⌊(L/8)/B⌋ + L % 8, block (L/8) % B — so a
-  // filter's record is fetched into one L2 instead of eight. Placement only changes speed.
-  int fb = blockIdx.y, bx = blockIdx.x;
-  if (xcd_b > 0) {
-    const int L = blockIdx.x, j = L >> 3;
-    fb = (L & 7) + 8 * (j / xcd_b);
-    bx = j % xcd_b;
-  }
-  // the previous chunk's Σ pass ended before this launch (same stream): its epoch, for the chains
-  if (A.pub_sigma && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
-    epoch_store(A.sync + kSyncSigma, A.pub_sigma);
-  if (kDiagBuild && (A.dbg & 1)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  if (fb >= nf) return;
-  const MsgDesc& d = A.desc[fb];
-  if (!(d.flags & kActive)) return;
-  const int f = A.f0 + fb;
-  const int tid = threadIdx.x;
-  if ((kDiagBuild && (A.dbg & 4)) && tid == 0 &&
-      static_cast<int>(epoch_load(A.sync + kSyncChain + f) - (A.seq + 1u)) < 0)
-    atomicAdd(A.sync + kSyncDbg + 1, 1u);
-  if ((kDiagBuild && (A.dbg & 8)) && tid == 0 && bx == 0) dbg_seq_check(A, 1, f, A.seq + 1u);
-  const ChunkRec* rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
-  // the chain of this chunk runs on the other stream: wait for its record
-  if (A.polls && tid == 0 && !epoch_wait_acquire(A.sync + kSyncChain + f, A.seq + 1u))
-    flag_timeout(&A.ctl[f].status, A.fatal);
-  drain_stores();
-  __syncthreads();
-  factor_record(rec, sh, tid);
-  __syncthreads();
-  if ((kDiagBuild && (A.dbg & 16)) && bx == 0) {  // the record as this kernel read it
-    unsigned long long s1 = 0;
-    for (int e = tid; e < kMaxU * ZC; e += 256) s1 += dbits(sh.Z[e / ZC][e % ZC]);
-    for (int e = tid; e < kMaxU * kZC; e += 256) s1 += dbits(sh.Y[e / kMaxU][e % kMaxU]);
-    if (tid < kMaxU)
-      s1 += static_cast<unsigned>(sh.u[tid]) + dbits(sh.alphaU[tid]) + dbits(sh.row0raw[tid]) +
-            dbits(sh.col0raw[tid]) + dbits(sh.Zx[tid]) + dbits(sh.xU[tid]);
-    if (tid == 0) s1 += dbits(sh.a1) + dbits(sh.a2) + dbits(sh.s00) + static_cast<unsigned>(sh.nu);
-    dlog_add(A, 4, A.seq, f, 1, s1);
-    if (tid < static_cast<int>(sizeof(MsgDesc) / 8))
-      dlog_add(A, 4, A.seq, f, 0, reinterpret_cast<const unsigned long long*>(&d)[tid]);
-  }
-  factor_wave<T, J>(A, d, f, bx * (blockDim.x >> 6) + (tid >> 6), sh, tid & 63);
-  if (kDiagBuild && (A.dbg & 2)) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-}
-
-// ---- Σ pass on MFMA -------------------------------------------------------------------------
-// Σ_out = Σ_in + Q̄ − Σ_k Kcat[k]ᵀ ⊗ Mcat[k], one tile per wave, four waves per workgroup.
-//   fp32  32×32 tile, v_mfma_f32_32x32x2_f32: D[row = (r&3) + 8(r>>2) + 4(lane>>5)][col = lane&31]
-//         → each load / store instruction covers 2 rows × 128 B
-//   fp64  32×16 tile, two v_mfma_f64_16x16x4_f64 blocks: D[row = 16ti + (lane>>4) + 4r][col = lane&15]
-//         → 4 rows × 128 B per instruction
-// A/B lane maps: 16x16x4 A[i = lane&15][k = lane>>4]; 32x32x2 A[i = lane&31][k = lane>>5].
-// Memory goes through buffer descriptors with 32-bit offsets (no 64-bit address per load):
-//   - Σ: the wave's 32-row panel (up to row n); a row ≥ n lies past the end, a column ≥ n gets
-//     the offset kOOB, so the range check returns 0 for its loads and drops its stores (no masks,
-//     no waits);
-//   - Kcat / Mcat: the factor rows are uniform (SGPR soffset), the lane's column in voffset.
-// Order: operands (L2-hot) first, then Σ_in. The MFMAs start from zero as soon as the operands
-// land and run while Σ_in is still in flight; Σ_in (+ Q̄) is added once, before the store.
-typedef float f16v __attribute__((ext_vector_type(16)));
-constexpr unsigned kOOB = 0x80000000u;  // voffset past any Σ panel descriptor (32·ld·w < 2 GiB)
-
-
-template <typename T>
-struct SigmaTile;
-
-// The simple form's factor rank is at most 2 + 2·kMaxChunk = 34: 17 k-steps of the 32×32×2 MFMA.
-// (kw, the rank rounded up to 4 for the fp64 tiles, would make it 18, the last one on the two zero
-// rows 34–35.) A Joseph chunk's rank 2 + 4m ≤ 66 (kw ≤ 68) takes a second block of 17 k-steps
-// (KB = 2): the operand registers are loaded again for it, so the tile keeps its register count.
-constexpr int kSteps = (2 + 2 * kMaxChunk + 1) / 2;
-static_assert(kMaxKW <= 4 * kSteps, "Joseph rank within two blocks of fp32 k-steps");
-struct F32TileRegs {  // one fp32 tile's loads
-  float a[kSteps], b[kSteps], sv[16];
-};
-template <>
-struct SigmaTile<float> {
-  static constexpr int kRows = 32, kCols = 32;
-  // descriptors based at the wave's row panel: offsets stay 32-bit for any n (a filter's Σ may
-  // exceed 4 GiB), and the records end at row n
-  static __device__ __forceinline__ __amdgpu_buffer_rsrc_t panel(const float* S, int n, int ld,
-                                                                 int R0) {
-    return buf_rsrc(S + static_cast<size_t>(R0) * ld,
-                    static_cast<unsigned>(min(n - R0, kRows)) * ld * 4u);
-  }
-  static __device__ __forceinline__ unsigned soff(int n, int ld, int C0, int lane) {
-    const int col = C0 + (lane & 31);
-    return col < n ? static_cast<unsigned>(4 * (lane >> 5) * ld + col) * 4u : kOOB;
-  }
-  // every load of the tile: the operands (L2-hot) first, then Σ_in
-  static __device__ __forceinline__ void load(F32TileRegs& g, const float* Sin, const float* kc,
-                                              const float* mc, int n, int ld, int ldk, int R0,
-                                              int C0, int lane) {
-    load_ops(g, kc, mc, n, ldk, R0, C0, lane);
-    // keep the operand loads ahead of Σ_in's: the MFMAs then wait for vmcnt(16), not vmcnt(0)
-    __builtin_amdgcn_sched_barrier(0);
-    load_sig(g, Sin, n, ld, R0, C0, lane);
-  }
-  // block kb: factor rows 2·kSteps·kb + 2s + (lane ≥ 32)
-  static __device__ __forceinline__ void load_ops(F32TileRegs& g, const float* kc, const float* mc,
-                                                  int n, int ldk, int R0, int C0, int lane,
-                                                  int kb = 0) {
-    const int kr = lane >> 5, kcol = lane & 31;
-    const unsigned kbytes = static_cast<unsigned>(kMaxKW) * ldk * 4u;
-    const auto rk = buf_rsrc(kc, kbytes), rm = buf_rsrc(mc, kbytes);
-    const int k0 = 2 * kSteps * kb;
-    const unsigned ko = static_cast<unsigned>((k0 + kr) * ldk + R0 + kcol) * 4u;
-    const unsigned mo = static_cast<unsigned>((k0 + kr) * ldk + min(C0 + kcol, n - 1)) * 4u;
-    const unsigned kstep = 2u * ldk * 4u;
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) {
-      g.a[s] = ld_f32(rk, ko, s * kstep);
-      g.b[s] = ld_f32(rm, mo, s * kstep);
-    }
-  }
-  static __device__ __forceinline__ void load_sig(F32TileRegs& g, const float* Sin, int n, int ld,
-                                                  int R0, int C0, int lane) {
-    const auto rin = panel(Sin, n, ld, R0);
-    const unsigned so = soff(n, ld, C0, lane);
-    const unsigned rstride = static_cast<unsigned>(ld) * 4u;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) g.sv[r] = ld_f32(rin, so + ((r & 3) + 8 * (r >> 2)) * rstride, 0);
-  }
-  static __device__ __forceinline__ void run(const float* Sin, float* Sout, const float* kc,
-                                             const float* mc, int n, int ld, int ldk, int kw,
-                                             bool first, double qd, int R0, int C0, int lane,
-                                             float*) {
-    F32TileRegs g;
-    load(g, Sin, kc, mc, n, ld, ldk, R0, C0, lane);
-    finish(g, Sout, n, ld, kw, first, qd, R0, C0, lane);
-  }
-  // the MFMAs on the tile's operands, Σ_in − K·M (+ Q̄), the stores
-  // pm (≠ null: the chunk's record holds the chain's fp64 Σ[U, U], kPendValid): the first position
-  // in U of each tile row (pm[0..32)) and column (pm[32..64)), > kMaxU − 1 for none — those
-  // entries take the record's value instead (what k_patch_stage wrote after the pass before)
-  static __device__ __forceinline__ void finish(const F32TileRegs& g, float* Sout, int n, int ld,
-                                                int kw, bool first, double qd, int R0, int C0,
-                                                int lane, const int* pm = nullptr,
-                                                const ChunkRec* rec = nullptr) {
-    f16v acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    mma(g, kw, 0, acc);
-    store(g, acc, Sout, n, ld, first, qd, R0, C0, lane, pm, rec);
-  }
-  // the k-steps of one operand block (k0: its first factor row): every MFMA issued, factor rows
-  // ≥ kw (stale) zeroed by a select — a branch per k-step let the compiler sink each operand load
-  // into its branch behind a vmcnt(0)
-  static __device__ __forceinline__ void mma(const F32TileRegs& g, int kw, int k0, f16v& acc) {
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) {
-      const bool live = k0 + 2 * s < kw;
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(live ? g.a[s] : 0.0f, live ? g.b[s] : 0.0f, acc,
-                                                 0, 0, 0);
-    }
-  }
-  // Joseph: the two operand blocks (the first loaded before Σ_in, the second after its MFMAs)
-  static __device__ __forceinline__ void finish2(F32TileRegs& g, const float* kc, const float* mc,
-                                                 int ldk, float* Sout, int n, int ld, int kw,
-                                                 bool first, double qd, int R0, int C0, int lane,
-                                                 const int* pm, const ChunkRec* rec) {
-    f16v acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-    mma(g, kw, 0, acc);
-    load_ops(g, kc, mc, n, ldk, R0, C0, lane, 1);
-    mma(g, kw, 2 * kSteps, acc);
-    store(g, acc, Sout, n, ld, first, qd, R0, C0, lane, pm, rec);
-  }
-  static __device__ __forceinline__ void store(const F32TileRegs& g, const f16v& acc, float* Sout,
-                                               int n, int ld, bool first, double qd, int R0,
-                                               int C0, int lane, const int* pm,
-                                               const ChunkRec* rec) {
-    const int kr = lane >> 5, col = C0 + (lane & 31);
-    const auto rout = panel(Sout, n, ld, R0);
-    const unsigned so = soff(n, ld, C0, lane);
-    const unsigned rstride = static_cast<unsigned>(ld) * 4u;
-    const float* sv = g.sv;
-    SIG_STAMP(2);
-    const float q = static_cast<float>(qd);
-    if (!pm) {  // (two loops: the common one keeps the plain store sequence)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = R0 + (r & 3) + 8 * (r >> 2) + 4 * kr;
-        float v = sv[r] - acc[r];
-        if (first && row == col && row < 3) v += q;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rout,
-                                              so + ((r & 3) + 8 * (r >> 2)) * rstride, 0, 0);
-      }
-      return;
-    }
-    const int pc = pm[32 + (lane & 31)];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int rl = (r & 3) + 8 * (r >> 2) + 4 * kr, row = R0 + rl;
-      float v = sv[r] - acc[r];
-      if (first && row == col && row < 3) v += q;
-      const int pr = pm[rl];
-      if (pr < kMaxU && pc < kMaxU) v = static_cast<float>(rec->Pend[pr][pc]);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rout,
-                                            so + ((r & 3) + 8 * (r >> 2)) * rstride, 0, 0);
-    }
-  }
-};
-
-// fp64 tile of 32 × 16·TJ: TJ = 2 for a few filters (more waves per filter), TJ = 4 for swarms
-// (≥ 16 filters): the M operand rows are read once per 64 columns instead of per 32 — the
-// operand loads are the pass's VMEM bottleneck there (swarm pass 589 → 564 µs; one filter's pass
-// 5.2 → 7.6 µs, so it keeps TJ = 2)
-// 2 = nt: the swarm's 2.2 GB of Σ stream through HBM once per message (≫ the 256 MB MALL), so its
-// Σ_in loads and Σ_out stores skip cache retention — swarm 1.09e7 → 1.15e7 corrections/s
-// (profiles/r2/r2z_*, two alternating runs each). The MALL-resident single-filter tiles keep the default.
-#ifndef EKF_SIG_POL
-#define EKF_SIG_POL 2
-#endif
-// Symmetric: Σ_out is symmetric (Σ_in + Q̄ − Kcatᵀ·Mcat is, the predict's A·Σ·Aᵀ and every
-// correction's K·S·Kᵀ are), so an fp64 pass computes only the tiles holding an element on or above
-// the diagonal (first tile column of tile row tr: ⌊32·tr / kCols⌋) and writes every element (r, c),
-// r > c, as the mirror of (c, r): Σ_in is read in those tiles only (≈ 0.58 of Σ at the swarm's n),
-// the MFMA work of the strictly-lower tiles is skipped, and Σ_out stays exactly symmetric. The
-// mirror goes out through the wave's LDS (the tile transposed, then row by row: a direct
-// transposed store is 16 rows × 32 B per instruction, measured 1.5× slower than the whole pass).
-// Swarm pass 445 → 379 µs standalone, bit-identical in the upper triangle (tools/pass64_lab.hip).
-constexpr int kTS = 34;  // transposed tile row stride (doubles; 16 B aligned rows)
-template <int TJ_>
-struct SigmaTile64 {
-  static constexpr int TJ = TJ_;
-  // cache policy of the swarm tile's Σ_in loads / Σ_out stores (the swarm's Σ streams through HBM)
-  static constexpr int kPol = TJ == 4 ? EKF_SIG_POL : 0;
-  static constexpr int kRows = 32, kCols = 16 * TJ;
-  static constexpr int kLds = kCols * kTS;  // doubles of the wave's transposed tile
-  // KB operand blocks of 36 factor rows (Joseph: 2, rank 2 + 4m ≤ 66; the second block's operands
-  // reuse the first's registers after its MFMAs)
-  template <int KB = 1>
-  static __device__ __forceinline__ void run(const double* Sin, double* Sout, const double* kc,
-                                             const double* mc, int n, int ld, int ldk, int kw,
-                                             bool first, double q, int R0, int C0, int lane,
-                                             double* tT) {
-    const int kr = lane >> 4, kcol = lane & 15;
-    // descriptors based at the wave's row panel: offsets stay 32-bit for any n (a filter's Σ
-    // may exceed 4 GiB), and the records end at row n
-    const size_t pbase = static_cast<size_t>(R0) * ld;
-    const unsigned sbytes = static_cast<unsigned>(min(n - R0, kRows)) * ld * 8u;
-    const unsigned kbytes = static_cast<unsigned>(kMaxKW) * ldk * 8u;
-    const auto rin = buf_rsrc(Sin + pbase, sbytes), rout = buf_rsrc(Sout + pbase, sbytes);
-    // the mirror: rows C0 … C0 + kCols − 1 of Σ_out from column R0
-    const auto rmir = buf_rsrc(Sout + static_cast<size_t>(C0) * ld + R0,
-                               static_cast<unsigned>(min(n - C0, kCols)) * ld * 8u);
-    const auto rk = buf_rsrc(kc, kbytes), rm = buf_rsrc(mc, kbytes);
-    double a[2][9], b[TJ][9], sv[2][TJ][4];
-    const unsigned ko = static_cast<unsigned>(kr * ldk + R0 + kcol) * 8u;
-    unsigned mo[TJ], so[TJ];
-    const unsigned rstride = static_cast<unsigned>(ld) * 8u;
-#pragma unroll
-    for (int tj = 0; tj < TJ; ++tj) {
-      const int col = C0 + 16 * tj + kcol;
-      mo[tj] = static_cast<unsigned>(kr * ldk + min(col, n - 1)) * 8u;
-      so[tj] = col < n ? static_cast<unsigned>(kr * ld + col) * 8u : kOOB;
-    }
-    const unsigned kstep = 4u * ldk * 8u;
-    auto load_ops = [&](int kb) {
-#pragma unroll
-      for (int s = 0; s < 9; ++s) {
-        a[0][s] = ld_f64(rk, ko, (9 * kb + s) * kstep);
-        a[1][s] = ld_f64(rk, ko + 16 * 8, (9 * kb + s) * kstep);
-#pragma unroll
-        for (int tj = 0; tj < TJ; ++tj) b[tj][s] = ld_f64(rm, mo[tj], (9 * kb + s) * kstep);
-      }
-    };
-    load_ops(0);
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < TJ; ++tj)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          sv[ti][tj][r] = __builtin_bit_cast(
-              double, __builtin_amdgcn_raw_buffer_load_b64(rin, so[tj] + (16 * ti + 4 * r) * rstride, 0, kPol));
-    d4 acc[2][TJ];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < TJ; ++tj) acc[ti][tj] = d4{0, 0, 0, 0};
-    auto mma = [&](int kb) {
-#pragma unroll
-      for (int s = 0; s < 9; ++s) {  // unconditional, stale rows ≥ kw zeroed (see the fp32 tile)
-        const bool live = 36 * kb + 4 * s < kw;
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-          for (int tj = 0; tj < TJ; ++tj)
-            acc[ti][tj] = mfma_f64(live ? a[ti][s] : 0.0, live ? b[tj][s] : 0.0, acc[ti][tj]);
-      }
-    };
-    mma(0);
-    if (KB == 2) {
-      load_ops(1);
-      mma(1);
-    }
-    SIG_STAMP(2);
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-      for (int tj = 0; tj < TJ; ++tj)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int rl = 16 * ti + kr + 4 * r, cl = 16 * tj + kcol;
-          const int row = R0 + rl, col = C0 + cl;
-          double v = sv[ti][tj][r] - acc[ti][tj][r];
-          if (first && row == col && row < 3) v += q;
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), rout,
-                                                col >= row ? so[tj] + (16 * ti + 4 * r) * rstride : kOOB,
-                                                0, kPol);
-          tT[cl * kTS + rl] = v;
-        }
-    // the mirror, two rows of the transposed tile per store (LDS in order within the wave)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    const int rl = lane & 31;
-#pragma unroll
-    for (int i = 0; i < kCols / 2; ++i) {
-      const int cl = 2 * i + (lane >> 5);
-      const double v = tT[cl * kTS + rl];
-      const int row = R0 + rl, col = C0 + cl;
-      const unsigned mo2 = col > row && col < n ? static_cast<unsigned>(cl * ld + rl) * 8u : kOOB;
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), rmir, mo2, 0, kPol);
-    }
-  }
-};
-// the tiles of a symmetric pass: tile row tr holds tile columns ⌊32·tr / kCols⌋ … tcols − 1
-template <int kCols>
-__host__ __device__ inline int sym_first(int tr) { return 32 * tr / kCols; }
-template <int kCols>
-__host__ __device__ inline int sym_tiles(int trows, int tcols) {
-  int t = 0;
-  for (int tr = 0; tr < trows; ++tr) t += tcols - sym_first<kCols>(tr);
-  return t;
-}
-// the t-th of them, row-major (wave-uniform t: a scalar walk over the tile rows)
-template <int kCols>
-__device__ __forceinline__ bool sym_tile(int t, int trows, int tcols, int& tr, int& tc) {
-  int base = 0;
-  for (tr = 0; tr < trows; ++tr) {
-    const int c = tcols - sym_first<kCols>(tr);
-    if (t < base + c) break;
-    base += c;
-  }
-  tc = tr < trows ? sym_first<kCols>(tr) + (t - base) : 0;
-  return tr < trows;
-}
-template <>
-struct SigmaTile<double> : SigmaTile64<2> {};
-// the tile a Σ pass of T runs: WIDE (swarms) takes the 32 × 64 fp64 tile
-template <typename T, bool WIDE>
-using PassTile = typename std::conditional<sizeof(T) == 8 && WIDE, SigmaTile64<4>, SigmaTile<T>>::type;
-
-// xcd_b = 0: grid (blocks per filter, filters). xcd_b = B > 0 (many filters): a 1-D grid whose
-// block L runs on XCD L % 8 (dispatch deals blocks round-robin over the XCDs); it is given filter
-// 8·⌊(L/8)/B⌋ + L % 8, tile block (L/8) % B, so all of a filter's blocks share one XCD and its
-// Kcat/Mcat are fetched into one L2 instead of eight. Placement only changes speed.
-// Waves take tiles row-major over a trows × tcols grid.
-// xcd_b = −1 (few filters, one per blockIdx.y): the tile grid is cut 2 × 4 into regions, block L
-// takes region L % 8 (so XCD L % 8 does): each XCD's L2 then fetches half of Kcat and a quarter
-// of Mcat instead of both whole (the fetch beyond Σ: 8 × (Kcat + Mcat) → 4 × Kcat + 2 × Mcat).
-constexpr int kRegRows = 2, kRegCols = 4;
-__host__ __device__ inline int region_tiles(int trows, int tcols) {  // the largest region's tiles
-  return ((trows + kRegRows - 1) / kRegRows) * ((tcols + kRegCols - 1) / kRegCols);
-}
-// An explicit occupancy target (the one the registers allowed anyway: 2 waves/SIMD for the wide
-// fp64 tile, 4–5 for the narrow one, 6–7 for fp32) makes the allocator keep the MFMA accumulators
-// in VGPRs instead of AGPRs (no v_accvgpr_read before the Σ_in subtraction and the stores): swarm
-// message 0.719 → 0.703 ms, N = 1024 fp64 pass 16.4 → 15.9 µs, fp32 unchanged
-// (profiles/r3/p3r_vgpr_acc_ab.txt, two alternating runs each)
-// KB: operand blocks of the rank (the Joseph form's instantiation: 2)
-template <typename T, bool WIDE, int KB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 2 : (sizeof(T) == 8 ? 4 : 6)))) void k_sigma_pass(PassArgs<T> A, int tcols, int xcd_b, int nf) {
-  using Tile = PassTile<T, WIDE>;
-  SIG_STAMP(0);
-  if (kDiagBuild && (A.dbg & 1)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  int fb = blockIdx.y, bx = blockIdx.x;
-  if (xcd_b > 0) {
-    const int L = blockIdx.x, j = L >> 3;
-    fb = (L & 7) + 8 * (j / xcd_b);
-    bx = j % xcd_b;
-    if (fb >= nf) return;
-  }
-  const MsgDesc& d = A.desc[fb];
-  constexpr bool kSym = sizeof(T) == 8;  // fp64: the symmetric tiles (SigmaTile64)
-  __shared__ int cmap[4][64];  // per wave (fp32 patch): tile row / column → first position in U
-  __shared__ double tT[kSym ? 4 : 1][kSym ? 16 * (WIDE ? 4 : 2) * kTS : 1];  // (SigmaTile64::kLds)
-  const int lane = threadIdx.x & 63;
-  const int trows = (A.n + Tile::kRows - 1) / Tile::kRows;
-  // the wave's tile index, provably wave-uniform (readfirstlane): the buffer descriptors built
-  // from it stay in SGPRs instead of a waterfall loop around every buffer access
-  int t = __builtin_amdgcn_readfirstlane(bx * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  int tr = 0, tc = 0;
-  bool ok;
-  if constexpr (kSym) {
-    // the upper tiles row-major; xcd_b < 0: XCD x takes the x-th eighth of them
-    if (xcd_b < 0) {
-      const int x = blockIdx.x & 7, w = (blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-      const int T8 = sym_tiles<Tile::kCols>(trows, tcols);
-      const int lo = x * T8 / 8, hi = (x + 1) * T8 / 8;
-      t = __builtin_amdgcn_readfirstlane(lo + w);
-      ok = t < hi;
-    } else {
-      ok = true;
-    }
-    ok = ok && sym_tile<Tile::kCols>(t, trows, tcols, tr, tc);
-  } else if (xcd_b < 0) {
-    const int x = blockIdx.x & 7, w = (blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int hx = x / kRegCols, qx = x % kRegCols;
-    const int r0 = hx * trows / kRegRows, r1 = (hx + 1) * trows / kRegRows;
-    const int c0 = qx * tcols / kRegCols, c1 = (qx + 1) * tcols / kRegCols;
-    const int cw = c1 - c0;
-    const int tt = __builtin_amdgcn_readfirstlane(w);
-    ok = tt < (r1 - r0) * cw;
-    tr = r0 + tt / cw;
-    tc = c0 + tt % cw;
-  } else {
-    ok = t < trows * tcols;
-    tr = t / tcols;
-    tc = t - tr * tcols;
-  }
-  if constexpr (std::is_same<Tile, SigmaTile<float>>::value) {
-    // fp32: the operand loads depend only on the filter and the tile, so they go out before the
-    // descriptor's scalar round trips (flags, parity, m, then the Σ pointer it selects) instead of
-    // behind them (≈ 0.3 µs of a 9 µs pass, tools/pass_lab.hip)
-    if (!ok) return;
-    const int f = A.f0 + fb;
-    // the patch test's record flags of both parities, issued with the operands (not a scalar round
-    // trip behind the descriptor's parity: that wait cost ≈ 0.4 µs of the pass)
-    const int rf0 = A.rec[f].flags, rf1 = A.rec[A.rec_stride + f].flags;
-    F32TileRegs g;
-    Tile::load_ops(g, A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.n, A.ldk,
-                   tr * Tile::kRows, tc * Tile::kCols, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    if (d.flags & kActive) {
-      SIG_STAMP(1);
-      const int kw = ((2 + ((d.flags & kJoseph) ? 4 : 2) * d.m + 3) / 4) * 4;
-      Tile::load_sig(g, A.sig[d.parity] + f * A.sig_stride, A.n, A.ld, tr * Tile::kRows,
-                     tc * Tile::kCols, lane);
-      // the fp32 patch (see k_patch_stage): the chain's fp64 Σ[U, U] over this tile's entries
-      // there, for the chunks that initialised a landmark (the pass's 1e7 − (1e7 − δ) loses δ)
-      const ChunkRec* rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
-      const int* pm = nullptr;
-      if ((d.parity ? rf1 : rf0) & kPendValid) {  // wave-uniform
-        const int R0 = tr * Tile::kRows, C0 = tc * Tile::kCols;
-        int* map = cmap[threadIdx.x >> 6];
-        map[lane] = kMaxU;
-        const int nu = rec->nu, u = rec->u[min(lane, kMaxU - 1)];
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        if (lane < nu && u >= R0 && u < R0 + 32) atomicMin(&map[u - R0], lane);
-        if (lane < nu && u >= C0 && u < C0 + 32) atomicMin(&map[32 + u - C0], lane);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        pm = map;
-      }
-      if constexpr (KB == 1)
-        Tile::finish(g, A.sig[d.parity ^ 1] + f * A.sig_stride, A.n, A.ld, kw,
-                     (d.flags & kFirst) != 0, A.q, tr * Tile::kRows, tc * Tile::kCols, lane, pm,
-                     rec);
-      else
-        Tile::finish2(g, A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.ldk,
-                      A.sig[d.parity ^ 1] + f * A.sig_stride, A.n, A.ld, kw,
-                      (d.flags & kFirst) != 0, A.q, tr * Tile::kRows, tc * Tile::kCols, lane, pm,
-                      rec);
-    }
-  } else if ((d.flags & kActive) && ok) {
-    SIG_STAMP(1);
-    const int f = A.f0 + fb;
-    if ((kDiagBuild && (A.dbg & 8)) && t == 0 && lane == 0) dbg_seq_check(A, 2, f, A.seq + 1u);
-    // this filter's rank (Joseph: K·M and V·Kᵀ per marker); rows beyond are stale
-    const int kw = ((2 + ((d.flags & kJoseph) ? 4 : 2) * d.m + 3) / 4) * 4;
-    Tile::template run<KB>(A.sig[d.parity] + f * A.sig_stride, A.sig[d.parity ^ 1] + f * A.sig_stride,
-              A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.n, A.ld, A.ldk, kw,
-              (d.flags & kFirst) != 0, A.q, tr * Tile::kRows, tc * Tile::kCols, lane,
-              tT[threadIdx.x >> 6]);
-  }
-  if (kDiagBuild && (A.dbg & 2)) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  SIG_STAMP(3);
-}
-
-
-// Right behind the Σ pass on its stream, for chunks that stage (kStageOut, either dtype): the
-// rebuild operands of the filter's chunk after next (StageRec), gathered from the Σ_out / x_out
-// just completed — off the chain's critical path, where the same gather at the chain's start cost
-// ≈ 10 µs of a 47 µs message (≈ 1 900 scattered lines through one CU). One workgroup per filter.
-// The fp32 patch this kernel also did until round 4 — the chain's fp64 Σ[U, U] (rec->Pend, rounded
-// once) over the pass's values, because the pass's 1e7 − (1e7 − δ) at a first sighting (the
-// reference's prior, slam.cpp:130) loses δ in fp32 — now happens in the pass's tiles
-// (SigmaTile<float>::finish), so Σ_out is already patched here; the patch branches below are off.
-template <typename T>
-__global__ __launch_bounds__(256) void k_patch_stage(PassArgs<T> A) {
-  // (the fp32 patch itself now happens in the Σ pass's tiles, SigmaTile<float>::finish: the
-  // staging below reads the patched Σ_out)
-  constexpr bool kPatch = false;
-  const MsgDesc& d = A.desc[blockIdx.x];
-  const int flags = d.flags;
-  if (!(flags & kActive)) return;
-  const bool stage = (flags & kStageOut) != 0;
-  if (!kPatch && !stage) return;
-  const int f = A.f0 + blockIdx.x;
-  const int tid = threadIdx.x;
-  const ChunkRec* rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
-  // the chain wrote Pend only for chunks that initialised a landmark (k_chain: `pend`)
-  const bool patch = kPatch && (rec->flags & kPendValid);
-  if (!patch && !stage) return;
-  __shared__ int su[kMaxU];
-  __shared__ int sfirst[kMaxU];           // position is its index's first in this chunk's U
-  __shared__ double spend[kMaxU][kMaxU + 1];
-  __shared__ int sgu[kStW], sgp[kStW];    // staged chain's U and U' (columns)
-  __shared__ int sgfu[kStW], sgfp[kStW];  // their first positions in this chunk's U (patched), −1
-  // ---- one global round trip: the record's block and U, the staged chunks' ids ----
-  constexpr int kPer = (kMaxU * kMaxU + 255) / 256;
-  double pv[kPer];
-  if (patch) {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = min(tid + 256 * i, kMaxU * kMaxU - 1);
-      pv[i] = rec->Pend[e / kMaxU][e % kMaxU];
-    }
-  }
-  const int nu = rec->nu;
-  const int myu = rec->u[min(tid, kMaxU - 1)];
-  // stage threads: a = tid (U of the chunk after next) or tid − 64 (U', the next chunk's)
-  const bool isp = tid >= 64;
-  const int sa = isp ? tid - 64 : tid;
-  const int sm = isp ? d.stg_pm : d.stg_m;
-  const int sid = (isp ? d.stg_pids : d.stg_ids)[min(max(sa - 3, 0) >> 1, kMaxChunk - 1)];
-  if (tid < kMaxU) su[tid] = myu;
-  if (patch) {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = tid + 256 * i;
-      if (e < kMaxU * kMaxU) spend[e / kMaxU][e % kMaxU] = pv[i];
-    }
-  }
-  __syncthreads();
-  // ---- first positions: every lane takes all of U into registers (one LDS wait) ----
-  int uall[kMaxU];
-#pragma unroll
-  for (int k = 0; k < kMaxU; ++k) uall[k] = su[k];
-  if (tid < kMaxU) {
-    bool fp = tid < nu;
-#pragma unroll
-    for (int k = 0; k < kMaxU; ++k) fp = fp && !(k < tid && uall[k] == myu);
-    sfirst[tid] = fp;
-  }
-  if (stage && sa < kStW && (tid < kStW || (isp && tid < 64 + kStW))) {
-    int col = 0;
-    if (sa < 3) col = sa;
-    else if (sa < 3 + 2 * sm && sa < kMaxU)
-      // k_chain's A0 mapping: marker c → 3 + 2·id (+1), a bad id → slot 0's, padding → 0
-      col = (sid < 0 || sid >= A.N ? 3 : 3 + 2 * sid) + ((sa - 3) & 1);
-    int fpos = -1;  // the first position of col in this chunk's U = its patched entry
-    if (patch) {
-#pragma unroll
-      for (int k = kMaxU - 1; k >= 0; --k) fpos = (k < nu && uall[k] == col) ? k : fpos;
-    }
-    (isp ? sgp : sgu)[sa] = col;
-    (isp ? sgfp : sgfu)[sa] = fpos;
-  }
-  __syncthreads();
-  T* S = A.sig[d.parity ^ 1] + f * A.sig_stride;
-  if (patch) {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = tid + 256 * i, a = e / kMaxU, b = e % kMaxU;
-      if (e < kMaxU * kMaxU && sfirst[a] && sfirst[b])
-        S[static_cast<size_t>(su[a]) * A.ld + su[b]] = static_cast<T>(pv[i]);
-    }
-  }
-  if (!stage) return;
-  // ---- stage: the chunk after next's rebuild operands (the second global round trip) ----
-  const double* xo = A.x[d.parity ^ 1] + f * A.x_stride;
-  StageRec<T>* sg = A.stage + static_cast<size_t>(d.parity) * A.rec_stride + f;
-  // Σ_out[r][c] as the chain would read it after the patch (the load of a patched entry races
-  // the scatter above and is discarded)
-  auto val = [&](int r, int fr, int c, int fc) -> T {
-    const T g = S[static_cast<size_t>(r) * A.ld + c];
-    return (patch && fr >= 0 && fc >= 0) ? static_cast<T>(spend[fr][fc]) : g;
-  };
-  constexpr int kSPer = (kStW * kStW + 255) / 256;  // 6
-  T od[kSPer], orr[kSPer], oc[kSPer];
-#pragma unroll
-  for (int i = 0; i < kSPer; ++i) {
-    const int e = min(tid + 256 * i, kStW * kStW - 1);
-    const int a = min(e / kStW, kMaxU - 1), b = min(e % kStW, kMaxU - 1);
-    od[i] = val(sgu[a], sgfu[a], sgu[b], sgfu[b]);
-    orr[i] = val(sgu[a], sgfu[a], sgp[b], sgfp[b]);
-    oc[i] = val(sgp[b], sgfp[b], sgu[a], sgfu[a]);
-  }
-  const int t = min(tid, kMaxU - 1);
-  const int z = sgfu[0];  // position 0 of U is the pose θ column
-  const T r0u = val(0, z, sgu[t], sgfu[t]), c0u = val(sgu[t], sgfu[t], 0, z);
-  const T r0p = val(0, z, sgp[t], sgfp[t]), c0p = val(sgp[t], sgfp[t], 0, z);
-  const double xg = xo[sgu[t]];
-  if (tid < kStW) {
-    sg->r0u[tid] = static_cast<double>(r0u);
-    sg->c0u[tid] = static_cast<double>(c0u);
-    sg->r0p[tid] = static_cast<double>(r0p);
-    sg->c0p[tid] = static_cast<double>(c0p);
-    sg->xg[tid] = xg;
-  }
-#pragma unroll
-  for (int i = 0; i < kSPer; ++i) {
-    const int e = tid + 256 * i;
-    if (e < kStW * kStW) {
-      sg->v[0][e] = od[i];
-      sg->v[1][e] = orr[i];
-      sg->v[2][e] = oc[i];
-    }
-  }
-}
-
-// Σ-pass epoch for the chains on the other stream, launched right behind the Σ pass on its stream:
-// the kernel boundary's release has written the pass's Σ_out (and the factor kernel's x, Kcat,
-// Mcat) back before this store, so the pass itself keeps plain stores and no per-block release.
-__global__ void k_sigma_epoch(unsigned* sync, unsigned epoch) {
-  if (threadIdx.x == 0) epoch_store(sync + kSyncSigma, epoch);
-}
-
-// ---- association ------------------------------------------------------------------------------
-// slam.cpp:344-440 for the marker in desc.z[0]: d_k = νᵀψ_k⁻¹ν over the known landmarks k < counter
-// (predict folded in when pending), the new slot's d forced to the gate (:406-408), first-index
-// argmin (arma::index_min), then commit (new landmark written into x_in, counter++) or roll back.
-constexpr int kAssocThreads = 1024;  // one known landmark per lane up to counter 1024: the gathers
-                                     // of every landmark in flight in one round
-template <typename T>
-__global__ __launch_bounds__(kAssocThreads) void k_assoc(PassArgs<T> A) {
-  __shared__ double s_pose[3], s_a[2], s_P33[3][3];
-  __shared__ double s_bd[kAssocThreads / 64];
-  __shared__ int s_bk[kAssocThreads / 64];
-  __shared__ int s_abort;
-  const MsgDesc& d = A.desc[blockIdx.y];
-  if (!(d.flags & kActive) || d.m == 0) return;
-  const int f = A.f0 + blockIdx.y;
-  const int tid = threadIdx.x;
-  const int ld = A.ld;
-  const T* S = A.sig[d.parity] + f * A.sig_stride;
-  double* x = A.x[d.parity] + f * A.x_stride;
-  FilterCtl* ctl = A.ctl + f;
-  // device epochs: Σ_in and x are the last Σ pass's (bulk stream), its epoch A.need_sigma
-  if (A.polls && A.need_sigma) {
-    if (tid == 0 && !epoch_wait_acquire(A.sync + kSyncSigma, A.need_sigma))
-      flag_timeout(&ctl->status, A.fatal);
-    __syncthreads();
-  }
-  const unsigned s = ctl->counter;
-  const int slot = d.assoc_slot;
-  if (tid == 0) {
-    double a1, a2;
-    predicted_pose(ctl->tmo, d, x, s_pose, &a1, &a2);
-    s_a[0] = a1;
-    s_a[1] = a2;
-    double raw[3][3];
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b) raw[a][b] = static_cast<double>(S[a * ld + b]);
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b) {
-        const double aa = (d.flags & kFirst) ? alpha_of(a, a1, a2) : 0.0;
-        const double ab = (d.flags & kFirst) ? alpha_of(b, a1, a2) : 0.0;
-        double v = raw[a][b] + aa * raw[0][b];
-        v = v + (raw[a][0] + aa * raw[0][0]) * ab;
-        if ((d.flags & kFirst) && a == b) v += A.q;
-        s_P33[a][b] = v;
-      }
-    s_abort = 0;
-    if (s >= static_cast<unsigned>(A.N)) {  // the reference indexes state(3+2·counter) out of range
-      s_abort = 1;
-      atomicOr(&ctl->status, EKF_FLAG_RANGE_D);
-      ctl->assoc_j[slot] = -1;
-      ctl->assoc_new[slot] = 0;
-    }
-  }
-  __syncthreads();
-  if (s_abort) return;
-  const double z0 = d.z[0][0], z1 = d.z[0][1];
-  const double a1 = s_a[0], a2 = s_a[1];
-  const bool first = (d.flags & kFirst) != 0;
-  double bestd = INFINITY;
-  int bestk = INT_MAX;
-  for (unsigned k = tid; k < s; k += blockDim.x) {
-    const int j = 3 + 2 * static_cast<int>(k);
-    double P[5][5];
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b) P[a][b] = s_P33[a][b];
-    const double r0j0 = static_cast<double>(S[j]), r0j1 = static_cast<double>(S[j + 1]);
-    for (int a = 0; a < 3; ++a) {
-      const double aa = first ? alpha_of(a, a1, a2) : 0.0;
-      P[a][3] = static_cast<double>(S[a * ld + j]) + aa * r0j0;
-      P[a][4] = static_cast<double>(S[a * ld + j + 1]) + aa * r0j1;
-    }
-    for (int e = 0; e < 2; ++e) {
-      const T* row = S + static_cast<size_t>(j + e) * ld;
-      const double rj0 = static_cast<double>(row[0]);
-      for (int b = 0; b < 3; ++b) {
-        const double ab = first ? alpha_of(b, a1, a2) : 0.0;
-        P[3 + e][b] = static_cast<double>(row[b]) + rj0 * ab;
-      }
-      P[3 + e][3] = static_cast<double>(row[j]);
-      P[3 + e][4] = static_cast<double>(row[j + 1]);
-    }
-    const double dist = assoc_dist(P, s_pose, x[j], x[j + 1], z0, z1, A.r);
-    if (dist < bestd) {  // strict: first index kept, NaN never selected
-      bestd = dist;
-      bestk = static_cast<int>(k);
-    }
-  }
-  wave_argmin(bestd, bestk);  // 64 lanes, ties → lower index (DPP, ekf_math.hpp)
-  const int wv = tid >> 6;
-  if ((tid & 63) == 0) {
-    s_bd[wv] = bestd;
-    s_bk[wv] = bestk;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < static_cast<int>(blockDim.x >> 6); ++w)
-      if (s_bd[w] < bestd || (s_bd[w] == bestd && s_bk[w] < bestk)) {
-        bestd = s_bd[w];
-        bestk = s_bk[w];
-      }
-    // the new slot (index s, d = gate) wins only over a strictly larger existing minimum
-    if (!(bestd <= A.gate)) {
-      const int js = 3 + 2 * static_cast<int>(s);
-      x[js] = s_pose[1] + z0 * cos(z1 + s_pose[0]);      // slam.cpp:351-354
-      x[js + 1] = s_pose[2] + z0 * sin(z1 + s_pose[0]);
-      ctl->counter = s + 1;
-      ctl->assoc_j[slot] = static_cast<int>(s);
-      ctl->assoc_new[slot] = 1;
-    } else {
-      ctl->assoc_j[slot] = bestk;
-      ctl->assoc_new[slot] = 0;
-    }
-  }
-}
-
-template <typename T>
-__global__ void k_posterior(PassArgs<T> A, int nf) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= nf) return;
-  const MsgDesc& d = A.desc[k];
-  if (!(d.flags & kActive)) return;
-  const int f = A.f0 + k;
-  const double* x = A.x[d.parity] + f * A.x_stride;
-  FilterCtl* ctl = A.ctl + f;
-  const Pose2 tmo = compose(Pose2{x[0], x[1], x[2]}, inverse(Pose2{d.odom[0], d.odom[1], d.odom[2]}));
-  ctl->tmo[0] = tmo.theta;
-  ctl->tmo[1] = tmo.x;
-  ctl->tmo[2] = tmo.y;
-}
-
-template <typename T>
-__global__ void k_init_diag(T* sig, size_t stride, int n, int ld, double v, int nf) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x + 3;
-  if (i >= n) return;
-  for (int f = blockIdx.y; f < nf; f += gridDim.y)
-    sig[f * stride + static_cast<size_t>(i) * ld + i] = static_cast<T>(v);
-}
-
-// dev only (PassArgs::dbg & 16): one workgroup per filter sums what the surrounding kernels left in
-// memory (launch_dbg_sum's kinds), in stream order
-template <typename T>
-__global__ __launch_bounds__(256) void k_dbg_sum(PassArgs<T> A, int kind, int nf) {
-  const int fb = blockIdx.x;
-  if (fb >= nf) return;
-  const MsgDesc& d = A.desc[fb];
-  if (!(d.flags & kActive)) return;
-  const int f = A.f0 + fb, p = d.parity, n = A.n, tid = threadIdx.x;
-  unsigned long long s[6] = {0, 0, 0, 0, 0, 0};
-  if (kind == 1) {
-    const double* xo = A.x[p ^ 1] + f * A.x_stride;
-    for (int i = tid; i < n; i += 256) s[0] += dbits(xo[i]);
-    const int kw = ((2 + ((d.flags & kJoseph) ? 4 : 2) * d.m + 3) / 4) * 4;
-    const T* kc = A.kcat + f * A.km_stride;
-    const T* mc = A.mcat + f * A.km_stride;
-    for (int e = tid; e < kw * n; e += 256) {
-      const size_t o = static_cast<size_t>(e / n) * A.ldk + e % n;
-      s[1] += dbits(kc[o]);
-      s[2] += dbits(mc[o]);
-    }
-  } else if (kind == 2) {
-    const T* so = A.sig[p ^ 1] + f * A.sig_stride;
-    for (int e = tid; e < n * n; e += 256) s[0] += dbits(so[static_cast<size_t>(e / n) * A.ld + e % n]);
-  } else {
-    const T* sp = A.sig[p ^ 1] + f * A.sig_stride;
-    const T* si = A.sig[p] + f * A.sig_stride;
-    for (int e = tid; e < n * n; e += 256) {
-      const size_t o = static_cast<size_t>(e / n) * A.ld + e % n;
-      s[0] += dbits(sp[o]);
-      s[4] += dbits(si[o]);
-    }
-    const double* xp = A.x[p ^ 1] + f * A.x_stride;
-    const double* xi = A.x[p] + f * A.x_stride;
-    for (int i = tid; i < n; i += 256) {
-      s[1] += dbits(xp[i]);
-      s[5] += dbits(xi[i]);
-    }
-    const unsigned long long* rw = reinterpret_cast<const unsigned long long*>(
-        A.rec + static_cast<size_t>(p ^ 1) * A.rec_stride + f);
-    for (int e = tid; e < static_cast<int>(sizeof(ChunkRec) / 8); e += 256) s[2] += rw[e];
-    if (tid < 3) s[3] += dbits(A.ctl[f].tmo[tid]);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k)
-    if (s[k]) dlog_add(A, kind, A.seq, f, k, s[k]);
-}
-
-template <typename T>
-hipError_t launch_dbg_sum(const PassArgs<T>& a, int nf, int kind, hipStream_t s) {
-  hipLaunchKernelGGL(k_dbg_sum<T>, dim3(nf), dim3(256), 0, s, a, kind, nf);
-  return hipGetLastError();
-}
-template hipError_t launch_dbg_sum<double>(const PassArgs<double>&, int, int, hipStream_t);
-template hipError_t launch_dbg_sum<float>(const PassArgs<float>&, int, int, hipStream_t);
-
-// ---- launchers ------------------------------------------------------------------------------
-// With events, the launch carries them in its dispatch (hipExtLaunchKernelGGL): they time the
-// kernel's own execution, not the queueing / dispatch latency around it.
-template <typename K, typename... Args>
-void launch(K kernel, dim3 grid, dim3 block, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
-            Args... args) {
-  if (e0 && e1)
-    hipExtLaunchKernelGGL(kernel, grid, block, 0, s, e0, e1, 0, args...);
-  else
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
-}
-
 template <typename T>
 hipError_t launch_chain(const PassArgs<T>& a, int nf, int nchunks, hipStream_t s, hipEvent_t e0,
                         hipEvent_t e1) {
@@ -2976,106 +1707,9 @@ hipError_t launch_chain(const PassArgs<T>& a, int nf, int nchunks, hipStream_t s
          e1, a, nchunks);
   return hipGetLastError();
 }
-
-template <typename T>
-hipError_t launch_factors(const PassArgs<T>& a, int nf, hipStream_t s, hipEvent_t e0,
-                          hipEvent_t e1) {
-  const int per_filter = (factor_waves(a) + 3) / 4;
-  // (the Joseph form's instantiation: Z's 4m columns; a handle's chunks are all of its form)
-  auto k = a.joseph ? k_factors<T, true> : k_factors<T, false>;
-  if (nf >= 16) {  // XCD-aware 1-D grid, as the swarm's Σ pass
-    launch(k, dim3(8 * ((nf + 7) / 8) * per_filter), dim3(256), s, e0, e1, a, per_filter, nf);
-  } else {
-    launch(k, dim3(per_filter, nf), dim3(256), s, e0, e1, a, 0, nf);
-  }
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_sigma_pass(const PassArgs<T>& a, int nf, bool publish, bool stage, hipStream_t s,
-                             hipEvent_t e0, hipEvent_t e1) {
-  constexpr int wpb = 4;  // waves per workgroup
-  // the tiles per filter: all of them, or (fp64, symmetric) those on or above the diagonal
-  auto tiles = [](int trows, int tcols, auto tile) {
-    using Tile = decltype(tile);
-    return sizeof(T) == 8 ? sym_tiles<Tile::kCols>(trows, tcols) : trows * tcols;
-  };
-  if (nf >= 16) {  // XCD-aware 1-D grid (see k_sigma_pass), wide fp64 tiles
-    using Tile = PassTile<T, true>;
-    const int trows = (a.n + Tile::kRows - 1) / Tile::kRows;
-    const int tcols = (a.n + Tile::kCols - 1) / Tile::kCols;
-    const int per_filter = (tiles(trows, tcols, Tile{}) + wpb - 1) / wpb;
-    const dim3 grid(8 * ((nf + 7) / 8) * per_filter);
-    launch(a.joseph ? k_sigma_pass<T, true, 2> : k_sigma_pass<T, true, 1>, grid, dim3(64 * wpb), s, e0, e1, a, tcols, per_filter, nf);
-  } else {
-    using Tile = PassTile<T, false>;
-    const int trows = (a.n + Tile::kRows - 1) / Tile::kRows;
-    const int tcols = (a.n + Tile::kCols - 1) / Tile::kCols;
-    if (trows >= 2 * kRegRows && tcols >= 2 * kRegCols) {  // XCD regions (k_sigma_pass)
-      const int per_x = sizeof(T) == 8 ? (tiles(trows, tcols, Tile{}) + 7) / 8 : region_tiles(trows, tcols);
-      const dim3 grid(8 * ((per_x + wpb - 1) / wpb), nf);
-      launch(a.joseph ? k_sigma_pass<T, false, 2> : k_sigma_pass<T, false, 1>, grid, dim3(64 * wpb), s, e0, e1, a, tcols, -1, nf);
-    } else {
-      const int per_filter = (tiles(trows, tcols, Tile{}) + wpb - 1) / wpb;
-      const dim3 grid(per_filter, nf);
-      launch(a.joseph ? k_sigma_pass<T, false, 2> : k_sigma_pass<T, false, 1>, grid, dim3(64 * wpb), s, e0, e1, a, tcols, 0, nf);
-    }
-  }
-  if (stage) hipLaunchKernelGGL(k_patch_stage<T>, dim3(nf), dim3(256), 0, s, a);
-  // the pass's epoch (otherwise published by the next chunk's factor kernel, PassArgs::pub_sigma)
-  if ((publish && a.polls) || (a.dbg & 4))
-    hipLaunchKernelGGL(k_sigma_epoch, dim3(1), dim3(64), 0, s, a.sync, a.seq + 1u);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_assoc(const PassArgs<T>& a, int nf, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-  launch(k_assoc<T>, dim3(1, nf), dim3(kAssocThreads), s, e0, e1, a);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_posterior(const PassArgs<T>& a, int nf, hipStream_t s) {
-  hipLaunchKernelGGL(k_posterior<T>, dim3((nf + 63) / 64), dim3(64), 0, s, a, nf);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_init_diag(T* sig, size_t stride, int n, int ld, double v, int nf, hipStream_t s) {
-  hipLaunchKernelGGL(k_init_diag<T>, dim3((n + 255) / 256, nf < 65535 ? nf : 65535), dim3(256), 0,
-                     s, sig, stride, n, ld, v, nf);
-  return hipGetLastError();
-}
-
-// Diagnostics (ekf_debug_poison_lds): overwrite a workgroup's whole LDS allocation with a NaN bit
-// pattern. Launched over every CU several times, it leaves LDS the way an arbitrary previous kernel
-// may, so a kernel that reads LDS it never wrote shows it deterministically (tests/).
-__global__ __launch_bounds__(256) void k_poison_lds(unsigned long long pattern) {
-  extern __shared__ unsigned long long lds_poison[];
-  for (int e = threadIdx.x; e < kPoisonLdsBytes / 8; e += blockDim.x) lds_poison[e] = pattern;
-  __syncthreads();
-  // keep the stores: one lane publishes a word the compiler cannot prove dead
-  if (threadIdx.x == 0 && lds_poison[blockIdx.x % (kPoisonLdsBytes / 8)] == 0x1ull)
-    lds_poison[0] = 0;
-}
-
-hipError_t launch_poison_lds(unsigned long long pattern, int n_blocks, hipStream_t s) {
-  hipLaunchKernelGGL(k_poison_lds, dim3(n_blocks), dim3(256), kPoisonLdsBytes, s, pattern);
-  return hipGetLastError();
-}
-
-#define EKF_INSTANTIATE(T)                                                              \
-  template hipError_t launch_chain<T>(const PassArgs<T>&, int, int, hipStream_t, hipEvent_t,        \
-                                      hipEvent_t);                                                 \
-  template hipError_t launch_factors<T>(const PassArgs<T>&, int, hipStream_t, hipEvent_t,          \
-                                        hipEvent_t);                                               \
-  template hipError_t launch_sigma_pass<T>(const PassArgs<T>&, int, bool, bool, hipStream_t, hipEvent_t, \
-                                           hipEvent_t);                                            \
-  template hipError_t launch_assoc<T>(const PassArgs<T>&, int, hipStream_t, hipEvent_t, hipEvent_t); \
-  template hipError_t launch_posterior<T>(const PassArgs<T>&, int, hipStream_t);              \
-  template hipError_t launch_init_diag<T>(T*, size_t, int, int, double, int, hipStream_t);
-EKF_INSTANTIATE(double)
-EKF_INSTANTIATE(float)
+template hipError_t launch_chain<double>(const PassArgs<double>&, int, int, hipStream_t, hipEvent_t,
+                                         hipEvent_t);
+template hipError_t launch_chain<float>(const PassArgs<float>&, int, int, hipStream_t, hipEvent_t,
+                                        hipEvent_t);
 
 }  // namespace ekfslam
-

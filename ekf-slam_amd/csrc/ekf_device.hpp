@@ -1,4 +1,5 @@
-// Device-side data layout shared by the kernels (ekf_kernels.hip) and the host runtime (ekf_api.cpp).
+// Device-side data layout shared by the kernels (ekf_chain.hip, ekf_factors.hip, ekf_sigma_pass.hip,
+// ekf_assoc.hip, ekf_resident.hip) and the host runtime (ekf_api.cpp).
 //
 // HBM layout per filter f (row-major, fp64 or fp32 per ekf_config.dtype):
 //   Σ[2]      : two n × ld ping-pong copies (ld = n rounded up to 128 bytes). One launch pair reads
@@ -29,8 +30,6 @@ constexpr int kSyncPlan = 32;    // (t, f) descriptors device replays have plann
                                  // its own 128-B line: the planner waves' fetch_adds do not contend
                                  // with the polls of the Σ epoch in word 0)
 constexpr int kSyncChain = 64;   // [F]: epoch of each filter's last complete chain
-constexpr int kSyncDbg = 48;     // dev only (PassArgs::dbg & 4): [0] chains, [1] factor kernels that
-                                 // started before their producer's epoch was visible, [2] checks
 
 // MsgDesc.flags
 constexpr int kFirst = 1;    // chunk carries the predict (slam.cpp:184-198) for this message

@@ -1,6 +1,9 @@
-// Kernel launchers (defined in ekf_kernels.hip, called by the host runtime in ekf_api.cpp).
+// Kernel launchers (each defined beside its kernel: ekf_chain.hip, ekf_factors.hip,
+// ekf_sigma_pass.hip, ekf_assoc.hip, ekf_resident.hip, plan_kernels.hip, ekf_small.hip; called by
+// the host runtime in ekf_api.cpp).
 // Optional e0/e1: timing events carried by the dispatch itself (kernel execution time).
 #pragma once
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -43,18 +46,19 @@ struct PassArgs {
   int n, ld, N, f0;
   double q, r, gate;
   int joseph;           // resident path: Joseph-form Σ update (ekf_set_joseph)
-  int dbg;              // dev only (EKF_DBG_ORDER >> 8, tools/diag_handover.py): 1 agent acquire at
-                        // the start of chain / factors / Σ pass, 2 agent release at their end,
-                        // 4 count hand-offs whose producer epoch is not yet visible (sync[48..]),
-                        // 8 check launch epochs, 16 chain / factor kernels log checksums (dlog), 32 k_dbg_sum
-                        // kernels around them (EKF_DBG_ORDER 8192)
-  unsigned long long* dlog;  // dev only: [kDlogKinds][64 seq][64 filters][8 slots] wrapping sums
 };
-constexpr int kDlogKinds = 21;  // 0 chain, 1-3 k_dbg_sum, 4 factor kernel, 5 + c chain step c
-// dev only: checksums of what a kernel pair left in memory (kind 1: after the factor kernel, x_out
-// Kcat Mcat; 2: after the Σ pass, Σ_out; 3: before the chain, Σ_in' x_in' record' tmo Σ_in x_in)
-template <typename T>
-hipError_t launch_dbg_sum(const PassArgs<T>& a, int n_filters, int kind, hipStream_t s);
+
+// What every launcher below calls. With events, the launch carries them in its dispatch
+// (hipExtLaunchKernelGGL): they time the kernel's own execution, not the queueing / dispatch
+// latency around it.
+template <typename K, typename... Args>
+void launch(K kernel, dim3 grid, dim3 block, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
+            Args... args) {
+  if (e0 && e1)
+    hipExtLaunchKernelGGL(kernel, grid, block, 0, s, e0, e1, 0, args...);
+  else
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+}
 
 // Chain kernel: the chunk's sequential corrections on the |U|×|U| block (predict folded in),
 // one workgroup per filter → ChunkRec.

@@ -1,5 +1,6 @@
-// Device math shared by the EKF kernels (ekf_kernels.hip, ekf_resident.hip): the predict's
-// pose and At entries, refined reciprocals, the range-bearing model and the 2×2 inverse.
+// Device math shared by the EKF kernels (ekf_chain.hip, ekf_factors.hip, ekf_sigma_pass.hip,
+// ekf_assoc.hip, ekf_resident.hip): the predict's pose and At entries, refined reciprocals, the
+// range-bearing model, the 2×2 inverse and the f64 MFMA.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,13 @@ namespace ekfslam {
 
 #define EKF_FLAG_RANGE_D 1u
 #define EKF_FLAG_NUMERIC_D 2u
+
+// f64 MFMA 16×16×4: A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15],
+// D[row = (lane>>4) + 4r][col = lane&15] (the f64 C/D map differs from the f32 one).
+typedef double d4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
+  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+}
 
 __device__ __forceinline__ double alpha_of(int idx, double a1, double a2) {
   return idx == 1 ? a1 : (idx == 2 ? a2 : 0.0);

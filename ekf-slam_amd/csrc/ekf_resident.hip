@@ -1,6 +1,6 @@
 // Register-resident filter kernel (gfx950) for small maps: n = 3 + 2N ≤ kResidentMaxN, fp64.
 //
-// The low-rank pipeline of ekf_kernels.hip (chain → factors → Σ pass per chunk, an association
+// The low-rank pipeline of ekf_chain.hip (chain → factors → Σ pass per chunk, an association
 // kernel per marker) is built for covariances that live in HBM. At the reference's own map size
 // (N = 50 slots, n = 103: basic_world and the rosbag drive, BASELINE configs[0] and [4]) the whole
 // Σ is 83 KB, and that pipeline is launch- and hand-off-bound (≈ 94 µs per associated marker).

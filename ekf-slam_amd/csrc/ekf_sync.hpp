@@ -1,6 +1,15 @@
-// Device helpers shared by the filter kernels (ekf_kernels.hip, ekf_assoc.hip): the cross-queue /
-// inter-workgroup hand-off protocol and buffer-descriptor loads. Included inside namespace ekfslam.
+// Device helpers shared by the filter kernels (ekf_chain.hip, ekf_factors.hip, ekf_sigma_pass.hip,
+// ekf_assoc.hip): the cross-queue / inter-workgroup hand-off protocol, the LDS-only barrier and
+// buffer-descriptor loads. Included inside namespace ekfslam.
 #pragma once
+
+// A workgroup barrier that orders LDS only: global loads and stores in flight stay in flight
+// across it (__syncthreads waits vmcnt(0), which counts both).
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 
 // ---- cross-queue hand-offs (chain on the main stream, factors + Σ pass on the bulk stream) ----
 // Protocol of cdna_hip_programming.md §6 Guideline 16: the producer stores its payload write-through

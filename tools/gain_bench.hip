@@ -1,7 +1,8 @@
 // Dev tool (not shipped): times the gain kernel alone and prints per-phase s_memtime stamps of
 // block (0,0) thread 0. Build: hipcc -O3 --offload-arch=gfx950 -DEKF_DIAG_STAMPS -I../include
 //   -I../ekf-slam_amd/csrc gain_bench.hip -o gain_bench
-#include "../ekf-slam_amd/csrc/ekf_kernels.hip"
+#include "../ekf-slam_amd/csrc/ekf_chain.hip"
+#include "../ekf-slam_amd/csrc/ekf_factors.hip"
 
 #include <cstdio>
 #include <cstdlib>

@@ -1,7 +1,7 @@
 // Dev tool (not shipped): Σ-pass variants A/B'd standalone against the product's k_sigma_pass on the
 // same buffers (N = 1024 fp32, the headline's pass), outputs compared bit for bit.
 // Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../include -I../ekf-slam_amd/csrc pass_lab.hip -o pass_lab
-#include "../ekf-slam_amd/csrc/ekf_kernels.hip"
+#include "../ekf-slam_amd/csrc/ekf_sigma_pass.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -570,7 +570,7 @@ int main(int argc, char** argv) {
   std::vector<float> ref(stride), out(stride);
   auto prod = [&](hipStream_t st) {
     const int trows = (n + 31) / 32, tcols = trows;
-    hipLaunchKernelGGL((k_sigma_pass<float, false>), dim3(8 * ((region_tiles(trows, tcols) + 3) / 4), 1),
+    hipLaunchKernelGGL((k_sigma_pass<float, false, 1>), dim3(8 * ((region_tiles(trows, tcols) + 3) / 4), 1),
                        dim3(256), 0, st, a, tcols, -1, 1);
   };
   struct V { const char* name; void (*fn)(const PassArgs<float>&, hipStream_t); };

@@ -1,6 +1,6 @@
 // Dev tool (not shipped): Σ-pass bandwidth vs a plain vectorised copy of the same bytes.
 // Build: hipcc -O3 --offload-arch=gfx950 -I../include -I../ekf-slam_amd/csrc sigma_bench.hip
-#include "../ekf-slam_amd/csrc/ekf_kernels.hip"
+#include "../ekf-slam_amd/csrc/ekf_sigma_pass.hip"
 
 #include <cstdio>
 #include <cstring>

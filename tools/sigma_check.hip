@@ -1,7 +1,7 @@
 // Dev tool (not shipped): the fp32 / fp64 Σ pass against a CPU Σ_in + Q̄ − Kcatᵀ·Mcat on random
 // operands; prints the max error and the first wrong element.
 // Build: hipcc -O3 --offload-arch=gfx950 -I../include -I../ekf-slam_amd/csrc sigma_check.hip
-#include "../ekf-slam_amd/csrc/ekf_kernels.hip"
+#include "../ekf-slam_amd/csrc/ekf_sigma_pass.hip"
 
 #include <cmath>
 #include <cstdio>
