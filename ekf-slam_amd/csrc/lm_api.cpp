@@ -1,5 +1,6 @@
 // Host runtime behind include/landmarks.h: device buffers, the handle's stream and the batched
-// laserCallback (nuslam/src/landmarks.cpp:109-156) over lm_kernels.hip.
+// laserCallback (nuslam/src/landmarks.cpp:109-156) over lm_kernels.hip, and the simulated laser
+// (nusim/src/nusim.cpp:559-710) over lidar_kernels.hip whose scans it can detect on in place.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -25,6 +26,15 @@ struct lm_ctx {
   double* d_out = nullptr;
   size_t cap_c = 0, cap_p = 0;
   bool timed = false;
+  // lm_simulate: inputs on the device (the scenes grown on demand), the upload's event, the
+  // kernel's timing events, and the scans resident in d_ranges
+  double* d_poses = nullptr;
+  int* d_scene = nullptr;
+  double* d_circles = nullptr;
+  size_t cap_circles = 0;  // doubles d_circles holds
+  hipEvent_t e_up = nullptr, s0 = nullptr, s1 = nullptr;
+  bool sim_timed = false;
+  int res_scans = 0, res_beams = 0;  // 0: nothing resident
 };
 
 namespace {
@@ -60,6 +70,32 @@ int stage_clusters(lm_t h, int nc, const int* offs, const double* xy) {
   return EKF_OK;
 }
 
+// Landmarks::laserCallback over the S × B ranges (and angles) already in the handle's buffers.
+int run_detect(lm_t h, int S, int B, double thr, lm_marker* markers, int max_markers,
+               int* counts) {
+  const int cap = max_markers > 0 ? max_markers : 1;
+  if (cap > h->marker_cap) {
+    if (grow(reinterpret_cast<void**>(&h->d_markers),
+             sizeof(lm_marker) * static_cast<size_t>(h->max_scans) * cap))
+      return EKF_E_NOMEM;
+    h->marker_cap = cap;
+  }
+  if (hipEventRecord(h->e0, h->stream) != hipSuccess) return EKF_E_HIP;
+  if (lmk::launch_detect(h->d_ranges, S, B, h->d_amin, h->d_ainc, thr, h->d_markers, cap,
+                         h->d_counts, h->work, h->stream) != hipSuccess)
+    return EKF_E_HIP;
+  if (hipEventRecord(h->e1, h->stream) != hipSuccess) return EKF_E_HIP;
+  h->timed = true;
+  if (hipMemcpyAsync(counts, h->d_counts, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream) !=
+      hipSuccess)
+    return EKF_E_HIP;
+  if (max_markers > 0 &&
+      hipMemcpyAsync(markers, h->d_markers, sizeof(lm_marker) * static_cast<size_t>(S) * cap,
+                     hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    return EKF_E_HIP;
+  return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+}
+
 }  // namespace
 
 extern "C" {
@@ -74,7 +110,9 @@ int lm_create(lm_t* out, int max_scans, int max_beams, int device) {
   h->device = device;
   const size_t S = max_scans;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess ||
-      hipEventCreate(&h->e0) != hipSuccess || hipEventCreate(&h->e1) != hipSuccess) {
+      hipEventCreate(&h->e0) != hipSuccess || hipEventCreate(&h->e1) != hipSuccess ||
+      hipEventCreate(&h->e_up) != hipSuccess || hipEventCreate(&h->s0) != hipSuccess ||
+      hipEventCreate(&h->s1) != hipSuccess) {
     lm_destroy(h);
     return EKF_E_HIP;
   }
@@ -82,6 +120,8 @@ int lm_create(lm_t* out, int max_scans, int max_beams, int device) {
       hipMalloc(&h->d_amin, sizeof(double) * S) != hipSuccess ||
       hipMalloc(&h->d_ainc, sizeof(double) * S) != hipSuccess ||
       hipMalloc(&h->d_counts, sizeof(int) * S) != hipSuccess ||
+      hipMalloc(&h->d_poses, sizeof(double) * 3 * S) != hipSuccess ||
+      hipMalloc(&h->d_scene, sizeof(int) * S) != hipSuccess ||
       hipMalloc(&h->work.px, sizeof(double) * S * max_beams) != hipSuccess ||
       hipMalloc(&h->work.py, sizeof(double) * S * max_beams) != hipSuccess ||
       hipMalloc(&h->work.cand, sizeof(lmk::Cand) * lmk::candidate_capacity(max_scans, max_beams)) !=
@@ -106,10 +146,12 @@ int lm_destroy(lm_t h) {
                   static_cast<void*>(h->d_xy), static_cast<void*>(h->d_out),
                   static_cast<void*>(h->work.px), static_cast<void*>(h->work.py),
                   static_cast<void*>(h->work.cand), static_cast<void*>(h->work.gcount),
-                  static_cast<void*>(h->work.sbase), static_cast<void*>(h->work.sncand)})
+                  static_cast<void*>(h->work.sbase), static_cast<void*>(h->work.sncand),
+                  static_cast<void*>(h->d_poses), static_cast<void*>(h->d_scene),
+                  static_cast<void*>(h->d_circles)})
     if (p) hipFree(p);
-  if (h->e0) hipEventDestroy(h->e0);
-  if (h->e1) hipEventDestroy(h->e1);
+  for (hipEvent_t e : {h->e0, h->e1, h->e_up, h->s0, h->s1})
+    if (e) hipEventDestroy(e);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
   return EKF_OK;
@@ -121,13 +163,7 @@ int lm_detect(lm_t h, int S, int B, const float* ranges, const double* amin, con
       !ainc || !counts || max_markers < 0 || (max_markers > 0 && !markers))
     return EKF_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
-  const int cap = max_markers > 0 ? max_markers : 1;
-  if (cap > h->marker_cap) {
-    if (grow(reinterpret_cast<void**>(&h->d_markers),
-             sizeof(lm_marker) * static_cast<size_t>(h->max_scans) * cap))
-      return EKF_E_NOMEM;
-    h->marker_cap = cap;
-  }
+  h->res_scans = h->res_beams = 0;  // the upload overwrites lm_simulate's scans
   const size_t nr = static_cast<size_t>(S) * B;
   if (hipMemcpyAsync(h->d_ranges, ranges, sizeof(float) * nr, hipMemcpyHostToDevice, h->stream) !=
           hipSuccess ||
@@ -136,20 +172,94 @@ int lm_detect(lm_t h, int S, int B, const float* ranges, const double* amin, con
       hipMemcpyAsync(h->d_ainc, ainc, sizeof(double) * S, hipMemcpyHostToDevice, h->stream) !=
           hipSuccess)
     return EKF_E_HIP;
-  if (hipEventRecord(h->e0, h->stream) != hipSuccess) return EKF_E_HIP;
-  if (lmk::launch_detect(h->d_ranges, S, B, h->d_amin, h->d_ainc, thr, h->d_markers, cap,
-                         h->d_counts, h->work, h->stream) != hipSuccess)
+  return run_detect(h, S, B, thr, markers, max_markers, counts);
+}
+
+void lm_scan_config_default(lm_scan_config* c) {
+  if (!c) return;
+  c->seed = 20240317ull;
+  c->scan0 = 0;
+  c->arena_w = 10.0;
+  c->arena_h = 5.0;
+  c->range_min = 0.11;
+  c->range_max = 10.0;
+  c->sigma = 0.0;
+}
+
+int lm_simulate(lm_t h, int S, int B, const double* poses, int G, int C, const double* circles,
+                const int* scene, const lm_scan_config* cfg, float* ranges_out) {
+  if (!h || S <= 0 || S > h->max_scans || B < 2 || B > h->max_beams || !poses || G < 1 || C < 0 ||
+      C > LM_MAX_CIRCLES || (C > 0 && !circles) || !cfg || !(cfg->sigma >= 0.0) ||
+      !(cfg->range_min <= cfg->range_max) || cfg->scan0 < 0)
+    return EKF_E_ARG;
+  for (int s = 0; scene && s < S; ++s)
+    if (scene[s] < 0 || scene[s] >= G) return EKF_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  h->res_scans = h->res_beams = 0;
+  const size_t nc = static_cast<size_t>(G) * C * 3;
+  if (nc > h->cap_circles) {
+    h->cap_circles = 0;
+    if (grow(reinterpret_cast<void**>(&h->d_circles), sizeof(double) * nc)) return EKF_E_NOMEM;
+    h->cap_circles = nc;
+  }
+  if (hipMemcpyAsync(h->d_poses, poses, sizeof(double) * 3 * S, hipMemcpyHostToDevice,
+                     h->stream) != hipSuccess ||
+      (nc && hipMemcpyAsync(h->d_circles, circles, sizeof(double) * nc, hipMemcpyHostToDevice,
+                            h->stream) != hipSuccess) ||
+      (scene && hipMemcpyAsync(h->d_scene, scene, sizeof(int) * S, hipMemcpyHostToDevice,
+                               h->stream) != hipSuccess) ||
+      hipEventRecord(h->e_up, h->stream) != hipSuccess)
     return EKF_E_HIP;
-  if (hipEventRecord(h->e1, h->stream) != hipSuccess) return EKF_E_HIP;
-  h->timed = true;
-  if (hipMemcpyAsync(counts, h->d_counts, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream) !=
-      hipSuccess)
+  lmk::ScanArgs a{};
+  a.poses = h->d_poses;
+  a.circles = h->d_circles;
+  a.scene = scene ? h->d_scene : nullptr;
+  a.ranges = h->d_ranges;
+  a.angle_min = h->d_amin;
+  a.angle_inc = h->d_ainc;
+  a.n_scans = S;
+  a.n_beams = B;
+  a.n_circles = C;
+  a.seed = cfg->seed;
+  a.scan0 = cfg->scan0;
+  a.arena_w = cfg->arena_w;
+  a.arena_h = cfg->arena_h;
+  a.range_min = cfg->range_min;
+  a.range_max = cfg->range_max;
+  a.sigma = cfg->sigma;
+  if (hipEventRecord(h->s0, h->stream) != hipSuccess ||
+      lmk::launch_scan(a, h->stream) != hipSuccess ||
+      hipEventRecord(h->s1, h->stream) != hipSuccess)
     return EKF_E_HIP;
-  if (max_markers > 0 &&
-      hipMemcpyAsync(markers, h->d_markers, sizeof(lm_marker) * static_cast<size_t>(S) * cap,
-                     hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+  h->sim_timed = true;
+  if (ranges_out) {
+    if (hipMemcpyAsync(ranges_out, h->d_ranges, sizeof(float) * static_cast<size_t>(S) * B,
+                       hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess)
+      return EKF_E_HIP;
+  } else if (hipEventSynchronize(h->e_up) != hipSuccess) {  // the caller's inputs are consumed
     return EKF_E_HIP;
-  return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  }
+  h->res_scans = S;
+  h->res_beams = B;
+  return EKF_OK;
+}
+
+int lm_detect_resident(lm_t h, double thr, lm_marker* markers, int max_markers, int* counts) {
+  if (!h || h->res_scans <= 0 || !counts || max_markers < 0 || (max_markers > 0 && !markers))
+    return EKF_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  return run_detect(h, h->res_scans, h->res_beams, thr, markers, max_markers, counts);
+}
+
+int lm_last_simulate_us(lm_t h, double* us) {
+  if (!h || !us || !h->sim_timed) return EKF_E_ARG;
+  float ms = 0.0f;
+  if (hipEventSynchronize(h->s1) != hipSuccess ||  // lm_simulate may have left the kernel in flight
+      hipEventElapsedTime(&ms, h->s0, h->s1) != hipSuccess)
+    return EKF_E_HIP;
+  *us = 1e3 * ms;
+  return EKF_OK;
 }
 
 int lm_fit_circles(lm_t h, int nc, const int* offs, const double* xy, double* out) {

@@ -40,4 +40,19 @@ hipError_t launch_fit(int n_clusters, const int* offsets, const double* xy, doub
 hipError_t launch_check(int n_clusters, const int* offsets, const double* xy, int* out,
                         hipStream_t st);
 
+// lm_simulate's kernel (lidar_kernels.hip): device pointers and the lm_scan_config by value.
+struct ScanArgs {
+  const double* poses;    // [S][3] body (θ, x, y)
+  const double* circles;  // [G][C][3] (x, y, r); unread when n_circles = 0
+  const int* scene;       // [S] in [0, G), nullptr: scene 0
+  float* ranges;          // [S][B] out
+  double* angle_min;      // [S] out: 0
+  double* angle_inc;      // [S] out: float32(2π/B)
+  int n_scans, n_beams, n_circles;  // n_circles ≤ LM_MAX_CIRCLES
+  unsigned long long seed;
+  long long scan0;
+  double arena_w, arena_h, range_min, range_max, sigma;
+};
+hipError_t launch_scan(const ScanArgs& a, hipStream_t st);
+
 }  // namespace lmk

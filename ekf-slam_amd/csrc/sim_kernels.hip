@@ -23,33 +23,15 @@
 #include "ekf_math.hpp"
 #include "geom.hpp"
 #include "sim_launch.hpp"
+#include "sim_rng.hpp"
 
 namespace ekfslam {
 namespace {
 
-constexpr unsigned long long kGolden = 0x9E3779B97F4A7C15ull;
 constexpr unsigned long long kSlipStream = 1, kNoiseStream = 2;  // synth._S_SLIP, _S_NOISE
 constexpr int kSenseNearest = 0, kSenseSurvey = 1, kSenseAll = 2;
 constexpr double kSurveyRange = 2.0;  // synth.SURVEY_RANGE
 constexpr int kPerLane = kSimMaxMap / 64;
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ double uniform(unsigned long long seed, unsigned long long stream,
-                                          unsigned long long idx) {
-  const unsigned long long key = mix64(seed * kGolden + stream);
-  return static_cast<double>(mix64(key + (idx + 1) * kGolden) >> 11) * 0x1p-53;
-}
-// N(0, 1) by Box–Muller from draws 2·idx, 2·idx + 1 (synth.rng_normal)
-__device__ __forceinline__ double normal(unsigned long long seed, unsigned long long stream,
-                                         unsigned long long idx) {
-  const double u1 = 1.0 - uniform(seed, stream, 2 * idx);
-  const double u2 = uniform(seed, stream, 2 * idx + 1);
-  return sqrt(-2.0 * log(u1)) * cos(2.0 * M_PI * u2);
-}
 
 __device__ __forceinline__ double bcast(double v, int l) { return __shfl(v, l, 64); }
 

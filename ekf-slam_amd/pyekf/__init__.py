@@ -43,6 +43,7 @@ EXPORTS = [
     "slam_odom", "slam_map_odom", "slam_filter", "slam_replay", "slam_integrate_odometry",
     "lm_create", "lm_destroy", "lm_detect", "lm_fit_circles", "lm_check_circles",
     "lm_last_kernel_us",
+    "lm_scan_config_default", "lm_simulate", "lm_detect_resident", "lm_last_simulate_us",
     "ekf_sim_config_default", "ekf_sim_create", "ekf_sim_destroy", "ekf_sim_run",
     "ekf_sim_markers", "ekf_sim_poses",
 ]
@@ -62,6 +63,13 @@ class SimConfig(C.Structure):
                 ("wheel_radius", C.c_double), ("track_width", C.c_double),
                 ("start_theta", C.c_double), ("start_x", C.c_double), ("start_y", C.c_double),
                 ("record", C.c_int)]
+
+
+class ScanConfig(C.Structure):
+    """lm_scan_config (include/landmarks.h)."""
+    _fields_ = [("seed", C.c_ulonglong), ("scan0", C.c_longlong),
+                ("arena_w", C.c_double), ("arena_h", C.c_double),
+                ("range_min", C.c_double), ("range_max", C.c_double), ("sigma", C.c_double)]
 
 
 class Config(C.Structure):
@@ -132,6 +140,10 @@ def lib():
             "lm_fit_circles": (_i, [_vp, _i, _vp, _vp, _vp]),
             "lm_check_circles": (_i, [_vp, _i, _vp, _vp, _vp]),
             "lm_last_kernel_us": (_i, [_vp, _dp]),
+            "lm_scan_config_default": (None, [C.POINTER(ScanConfig)]),
+            "lm_simulate": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, C.POINTER(ScanConfig), _vp]),
+            "lm_detect_resident": (_i, [_vp, _d, _vp, _i, _vp]),
+            "lm_last_simulate_us": (_i, [_vp, _dp]),
             "ekf_sim_config_default": (None, [C.POINTER(SimConfig)]),
             "ekf_sim_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(SimConfig), _i, _vp]),
             "ekf_sim_destroy": (_i, [_vp]),

@@ -1,14 +1,16 @@
 """ctypes wrapper of include/landmarks.h — the lidar landmark front-end (nuslam/src/landmarks.cpp,
-turtlelib/src/landmark_detection.cpp) on the GPU. Plumbing for tests and bench.py."""
+turtlelib/src/landmark_detection.cpp) and the simulated laser that can feed it
+(nusim/src/nusim.cpp:559-710) on the GPU. Plumbing for tests and bench.py."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from . import EKF_OK, EkfError, lib
+from . import EKF_OK, EkfError, ScanConfig, lib
 
 LM_MAX_BEAMS, LM_MAX_CLUSTER, LM_NO_BREAK = 2048, 39, -1
+LM_MAX_CIRCLES = 1024
 MARKER_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8"), ("r", "<f8"), ("id", "<i4"), ("pad", "<i4")])
 
 
@@ -30,6 +32,7 @@ class Detector:
 
     def __init__(self, max_scans=1, max_beams=360, device=0):
         self.h = C.c_void_p()
+        self._resident = 0  # scans the last simulate() left on the device
         _check(lib().lm_create(C.byref(self.h), max_scans, max_beams, device), "lm_create")
 
     def close(self):
@@ -79,6 +82,50 @@ class Detector:
         _check(lib().lm_check_circles(self.h, len(clusters), offs.ctypes.data, xy.ctypes.data,
                                       out.ctypes.data), "lm_check_circles")
         return out.astype(bool)
+
+    def simulate(self, poses, circles, scene=None, n_beams=360, ranges=True, **cfg):
+        """nusim's simulated laser on the device (lm_simulate): poses [S, 3] = (θ, x, y), circles
+        [C, 3] or [G, C, 3] = (x, y, r), scene [S] picks each scan's circle set (None: set 0).
+        ``cfg``: lm_scan_config fields (seed, scan0, arena_w, arena_h, range_min, range_max, sigma)
+        or ``arena=(w, h)``. The scans stay on the device for ``detect_resident``; returns them as
+        float32 [S, n_beams] too unless ``ranges`` is false (then nothing comes back to the host)."""
+        p = np.ascontiguousarray(np.atleast_2d(np.asarray(poses, dtype=np.float64)))
+        S = p.shape[0]
+        c = np.asarray(circles, dtype=np.float64)
+        c = np.ascontiguousarray(c.reshape((1, -1, 3)) if c.ndim < 3 else c)
+        G, Cn = c.shape[0], c.shape[1]
+        sc = None if scene is None else np.ascontiguousarray(scene, dtype=np.int32)
+        if sc is not None and sc.shape != (S,):
+            raise ValueError("scene must hold one index per scan")
+        k = ScanConfig()
+        lib().lm_scan_config_default(C.byref(k))
+        if "arena" in cfg:
+            k.arena_w, k.arena_h = cfg.pop("arena")
+        for name, v in cfg.items():
+            if name not in dict(ScanConfig._fields_):
+                raise TypeError(f"unknown scan setting {name!r}")
+            setattr(k, name, v)
+        out = np.zeros((S, n_beams), dtype=np.float32) if ranges else None
+        _check(lib().lm_simulate(self.h, S, n_beams, p.ctypes.data, G, Cn,
+                                 c.ctypes.data if c.size else None,
+                                 None if sc is None else sc.ctypes.data, C.byref(k),
+                                 None if out is None else out.ctypes.data), "lm_simulate")
+        self._resident = S
+        return out
+
+    def detect_resident(self, threshold=0.2, max_markers=32):
+        """``detect`` on the scans the last ``simulate`` left on the device (lm_detect_resident)."""
+        S = max(self._resident, 1)
+        out = np.zeros((S, max_markers), dtype=MARKER_DTYPE)
+        cnt = np.zeros(S, dtype=np.int32)
+        _check(lib().lm_detect_resident(self.h, threshold, out.ctypes.data, max_markers,
+                                        cnt.ctypes.data), "lm_detect_resident")
+        return cnt, out
+
+    def last_simulate_us(self):
+        us = C.c_double()
+        _check(lib().lm_last_simulate_us(self.h, C.byref(us)), "lm_last_simulate_us")
+        return us.value
 
     def last_kernel_us(self):
         us = C.c_double()

@@ -46,6 +46,7 @@ SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
 SURVEY_RANGE = 2.0  # survey messages sense out to this multiple of max_range
 # RNG streams
 _S_SLIP, _S_NOISE, _S_MAP, _S_SHUFFLE, _S_DELETE = 1, 2, 3, 4, 5
+_S_LIDAR = 6  # lidar_scans_counter / lm_simulate range noise
 
 
 @dataclass
@@ -499,6 +500,50 @@ def lidar_scans(poses, circles, arena=(10.0, 5.0), n_beams=360, sigma=0.0, seed=
     best = np.clip(best, range_min, range_max)
     if sigma > 0.0:
         best = best + np.random.default_rng(seed).normal(0.0, sigma, best.shape)
+    return best.astype(np.float32)
+
+
+def lidar_scans_counter(poses, circles, scene=None, arena=(10.0, 5.0), n_beams=360, sigma=0.0,
+                        seed=20240317, scan0=0, range_min=0.11, range_max=10.0):
+    """``lidar_scans`` with per-scan scenes and the counter-based RNG: the host restatement of the
+    device's simulated laser (lm_simulate, ekf-slam_amd/csrc/lidar_kernels.hip), which runs the
+    same arithmetic expression for expression.
+
+    ``circles`` is one scene [C, 3] = (x, y, r) or G scenes [G, C, 3]; ``scene`` [P] picks each
+    scan's (None: scene 0). The noise of beam b of scan s is σ × normal draw (scan0 + s)·n_beams + b
+    of stream 6 under ``seed``, so scans [k, P) of one call equal a second call on poses[k:] with
+    ``scan0=k``. With ``sigma=0`` nothing is drawn and the result is ``lidar_scans``' bit for bit."""
+    poses = np.atleast_2d(np.asarray(poses, dtype=np.float64))
+    P = poses.shape[0]
+    circ = np.asarray(circles, dtype=np.float64)
+    circ = circ.reshape((1, -1, 3)) if circ.ndim < 3 else circ
+    sel = np.zeros(P, dtype=np.intp) if scene is None else np.asarray(scene, dtype=np.intp)
+    if sel.shape != (P,) or (P and (sel.min() < 0 or sel.max() >= circ.shape[0])):
+        raise ValueError("scene must hold one index in [0, G) per scan")
+    mine = circ[sel]                                                    # [P, C, 3]
+    th = poses[:, 0:1] + np.arange(n_beams)[None, :] * (2.0 * math.pi / n_beams)
+    lx = (poses[:, 1] - 0.032 * np.cos(poses[:, 0]))[:, None]
+    ly = (poses[:, 2] - 0.032 * np.sin(poses[:, 0]))[:, None]
+    dx, dy = np.cos(th), np.sin(th)
+    best = np.full(th.shape, np.inf)
+    for c in range(mine.shape[1]):
+        cx, cy, r = mine[:, c, 0:1], mine[:, c, 1:2], mine[:, c, 2:3]
+        fx, fy = lx - cx, ly - cy
+        bq = fx * dx + fy * dy
+        disc = bq * bq - (fx * fx + fy * fy - r * r)
+        with np.errstate(invalid="ignore"):
+            t = -bq - np.sqrt(disc)
+        hit = (disc >= 0.0) & (t > 0.0)
+        best = np.where(hit, np.minimum(best, t), best)
+    hx, hy = arena[0] / 2.0, arena[1] / 2.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for den, lim, org in ((dx, hx, lx), (-dx, hx, -lx), (dy, hy, ly), (-dy, hy, -ly)):
+            best = np.where(den > 1e-12, np.minimum(best, (lim - org) / den), best)
+    best = np.clip(best, range_min, range_max)
+    if sigma > 0.0:
+        idx = ((np.uint64(scan0) + np.arange(P, dtype=np.uint64))[:, None] * np.uint64(n_beams) +
+               np.arange(n_beams, dtype=np.uint64)[None, :])
+        best = best + sigma * rng_normal(np.uint64(seed), _S_LIDAR, idx)
     return best.astype(np.float32)
 
 

@@ -5,6 +5,8 @@
  * `landmarks` node (nuslam/src/landmarks.cpp) and turtlelib's circle classification / fitting
  * (turtlelib/src/landmark_detection.cpp). Its MarkerArray output is what `slam`'s sensor_cb
  * consumes (ekf_sensor / slam_markers with SOURCE_ASSOC). SURVEY.md §8f row 1.
+ * Its input can be made on the device too: lm_simulate is nusim's simulated laser
+ * (nusim/src/nusim.cpp:559-710), and lm_detect_resident detects on its scans where they lie.
  *
  * Batched: one call takes S scans (independent robots / filters of a Monte-Carlo swarm, or
  * consecutive scans of one robot), one wavefront per scan on the GPU. Plain C types only; every
@@ -18,6 +20,7 @@ extern "C" {
 #endif
 
 #define LM_MAX_BEAMS 2048       /* beams per scan (LDS-resident)                           */
+#define LM_MAX_CIRCLES 1024     /* cylinders per simulated scene (LDS-resident)              */
 #define LM_MAX_CLUSTER 39       /* clusters of 4..39 points are fitted (landmarks.cpp:122)  */
 #define LM_NO_BREAK (-1)        /* per-scan count: the scan has no cluster break; the
                                    reference throws at clusters.at(0) (landmarks.cpp:94)    */
@@ -58,8 +61,41 @@ int lm_fit_circles(lm_t h, int n_clusters, const int* offsets, const double* xy,
  * Clusters need ≥ 3 points (the reference's angle vector has size − 2 entries). */
 int lm_check_circles(lm_t h, int n_clusters, const int* offsets, const double* xy, int* out);
 
-/* Per-kernel device time of the last lm_detect (HIP events around the dispatch), microseconds. */
+/* Per-kernel device time of the last lm_detect / lm_detect_resident (HIP events around the
+ * dispatch), microseconds. */
 int lm_last_kernel_us(lm_t h, double* us);
+
+/* nusim's simulated laser (publish_lidar_data, nusim/src/nusim.cpp:559-710) for S scans on the
+ * device: beam b of a scan taken at body pose (θ, x, y) leaves the lidar, mounted 0.032 m behind
+ * the body origin, along θ + b·2π/B; its range is the nearest hit among the scene's cylinders and
+ * the four walls of an axis-aligned arena centred on the origin, clamped to
+ * [range_min, range_max], plus sigma·N(0, 1), rounded to float. The normal draw of beam b of scan
+ * s is draw (scan0 + s)·B + b of stream 6 under `seed` (pyekf.synth's counter-based RNG), so a
+ * run split into several calls by scan0 gives the bits of one call; sigma = 0 draws nothing. */
+typedef struct {
+  unsigned long long seed; long long scan0;   /* draw index base, see above (>= 0) */
+  double arena_w, arena_h;                    /* default 10, 5 */
+  double range_min, range_max;                /* 0.11, 10.0 (nusim.cpp:570-571) */
+  double sigma;                               /* 0: noiseless (>= 0) */
+} lm_scan_config;
+void lm_scan_config_default(lm_scan_config*);
+
+/* poses[S][3]; circles[G][C][3]; scene[S] in [0,G) or NULL (all scans use scene 0).
+ * Leaves the scans resident in the handle (angle_min 0, angle_increment float32(2π/B) widened
+ * to double); ranges_out nullable: a host copy, which makes the call synchronous. Without it the
+ * call returns once the inputs are uploaded (they may be freed), the kernel still in flight on
+ * the handle's stream. n_circles = 0 (walls only) is valid, and then circles may be NULL.
+ * EKF_E_ARG: n_scans outside [1, max_scans], n_beams outside [2, max_beams], n_circles outside
+ * [0, LM_MAX_CIRCLES], n_scenes < 1, a scene index outside [0, n_scenes), a NULL poses / cfg (or
+ * circles with n_circles > 0), or a configuration with range_min > range_max. */
+int lm_simulate(lm_t h, int n_scans, int n_beams, const double* poses, int n_scenes,
+                int n_circles, const double* circles, const int* scene,
+                const lm_scan_config* cfg, float* ranges_out);
+/* lm_detect on the resident scans of the last lm_simulate: no range upload. EKF_E_ARG when
+ * nothing is resident (no lm_simulate yet, or an lm_detect since overwrote the range buffer). */
+int lm_detect_resident(lm_t h, double threshold, lm_marker* markers, int max_markers, int* counts);
+/* Device time of the last lm_simulate's kernel (HIP events around the dispatch), microseconds. */
+int lm_last_simulate_us(lm_t h, double* us);
 
 #ifdef __cplusplus
 }
