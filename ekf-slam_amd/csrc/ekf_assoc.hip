@@ -33,7 +33,7 @@
 //
 // The file's end holds the other unknown-association kernel, k_assoc: one marker per launch, each
 // followed by a single-marker chunk (chain, factors, Σ pass) — the route the host takes when
-// k_assoc_msg's workgroups cannot all be resident (ekf_api.cpp am_route) or with EKF_ASSOC_MSG=0.
+// k_assoc_msg's workgroups cannot all be resident (ekf_sched.cpp am_route) or with EKF_ASSOC_MSG=0.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 

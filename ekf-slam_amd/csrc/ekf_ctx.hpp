@@ -1,0 +1,151 @@
+// The handle behind include/ekf.h: device memory, the two HIP streams and what orders them, the
+// upload ring, profiling, and the host planner. Shared by the scheduler (ekf_sched.cpp) and the C
+// ABI (ekf_api.cpp), which also declares here what it calls of the scheduler.
+#pragma once
+#include <hip/hip_ext.h>
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "ekf.h"
+#include "ekf_device.hpp"
+#include "ekf_launch.hpp"
+#include "ekf_plan.hpp"
+
+namespace ekfslam {
+
+constexpr int kRing = 16;  // pinned staging slots (host may run this many uploads ahead)
+
+struct StageSlot {
+  MsgDesc* p = nullptr;
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  bool used = false;
+};
+
+struct ProfEvents {
+  std::vector<hipEvent_t> start, stop;
+};
+
+// What timed() brackets with events; the numerals are ekf_profile_read's `kind` (ABI).
+enum ProfSlot : int {
+  kProfSigma = 0,     // Σ pass
+  kProfChain = 1,     // chain (reported per chunk)
+  kProfAssoc = 2,     // association
+  kProfFactors = 3,   // factors
+  kProfResident = 4,  // resident filter kernel
+  kProfSlots = 5,
+};
+
+}  // namespace ekfslam
+
+static_assert(EKF_RESIDENT_MAX_N == ekfslam::kResidentMaxN, "ekf.h and ekf_launch.hpp agree");
+
+struct ekf_ctx {
+  ekf_config cfg{};
+  int n = 0, ld = 0, ldk = 0, F = 0;
+  size_t w = 8;
+  hipStream_t stream = nullptr;  // chain + factors (+ association, posterior)
+  hipStream_t bulk = nullptr;    // Σ passes: chunk t's pass overlaps chunk t+1's chain
+  bool serial = false;           // EKF_SERIAL=1: every kernel on one stream (per-dispatch PMC)
+  bool resident = false;         // n ≤ kResidentMaxN, fp64: Σ in registers (ekf_resident.hip)
+  bool defer = false;            // ekf_defer: plan now, upload and launch later
+  bool assoc_msg = true;         // unknown association by chunks (k_assoc_msg); EKF_ASSOC_MSG=0:
+                                 // one association kernel + launch pair per marker
+  bool main_dirty = false;       // work on the main stream since the bulk stream last joined it
+  bool main_unordered = false;   // the main stream ran descriptor-reading work (k_posterior) that
+                                 // nothing on the bulk stream is ordered after: a device planner
+                                 // on the bulk stream must wait for it before rewriting ddesc
+  bool epoch_owed = false;       // the last Σ pass published no device epoch (the flush's last
+                                 // launch: the next flush joins the bulk stream on the host)
+  ekfslam::AmArgs am{};          // k_assoc_msg scratch (allocated at the first association chunk)
+  int am_route = 0;              // unknown association: EKF_ASSOC_* (fixed at ekf_create)
+  int am_route_j = 0;            // ... for the Joseph-form kernel (its larger LDS may fit fewer)
+  int am_group = 1;              // filters per k_assoc_msg launch (co-resident, assoc_msg_group)
+  int am_group_j = 1;            // ... Joseph form
+  int bulk_cus_per_xcd = 0;      // CUs the bulk stream may use on each XCD
+  int main_cus_per_xcd = 0;      // CUs the main stream may use on each XCD (0: every CU, no mask)
+  unsigned* fatal_h = nullptr;   // host-mapped: a device poll timed out (EKF_E_TIMEOUT)
+  unsigned* fatal_d = nullptr;   // its device address (PassArgs::fatal)
+  hipEvent_t ev_chain = nullptr;          // main → bulk: the chunk's chain is done
+  hipEvent_t ev_join = nullptr;           // bulk → main: everything issued so far
+  bool devsync = false;                   // streams synchronise through device epochs
+  unsigned* sync = nullptr;               // device epochs: Σ pass done, its ticket, chains done
+  hipEvent_t ev_sig[2] = {nullptr, nullptr};  // bulk → main: Σ pass of launch s, by s & 1
+  long long seq = 0;                      // launch pairs issued
+  void* sig[2] = {nullptr, nullptr};
+  double* x[2] = {nullptr, nullptr};
+  void* kcat = nullptr;
+  void* mcat = nullptr;
+  ekfslam::FilterCtl* ctl = nullptr;
+  ekfslam::ChunkRec* rec = nullptr;
+  void* stage = nullptr; // StageRec<T>[2][F]: a kLook chain's rebuild operands (kStageIn)
+  ekfslam::MsgDesc* ddesc = nullptr;
+  size_t sig_stride = 0, x_stride = 0, km_stride = 0;
+  // ekf_replay_device: the planning state lives on the device while dev_plan (ping-pong by
+  // dstate_cur); the planner adopts it (adopt_device_plan) before it is used again
+  ekfslam::PlanState* dstate[2] = {nullptr, nullptr};
+  ekfslam::PlanState* hstate = nullptr;  // pinned: host → device and back
+  int dstate_cur = 0;
+  bool dev_plan = false;
+  hipStream_t plan_stream = nullptr;  // the stream the last device planner ran on
+  unsigned plan_total = 0;    // kSyncPlan: descriptors device planners have counted so far
+  unsigned need_plan = 0;     // the next chain launch polls kSyncPlan for this (0: none)
+  // the host mirror and the launch plan (ekf_set_joseph's form lives there too)
+  ekfslam::Planner plan;
+  std::vector<unsigned> held;    // status bits taken off the device word by the synchronous forms
+                                 // (take_numeric); ekf_get_status reports and clears them too
+  size_t ddesc_cap = 0;
+  // pinned staging ring (the host may run kRing uploads ahead of the device), every slot ring_cap
+  ekfslam::StageSlot ring[ekfslam::kRing];
+  size_t ring_cap = 0;
+  int ring_next = 0;
+  // profiling
+  bool prof = false;
+  ekfslam::ProfEvents pe[ekfslam::kProfSlots];
+  std::vector<hipEvent_t> pool;
+  long long prof_launches[ekfslam::kProfSlots] = {0, 0, 0, 0, 0};
+  long long prof_chunks = 0;  // chunks the timed chain launches walked
+  double prof_ms[ekfslam::kProfSlots] = {0, 0, 0, 0, 0};
+};
+
+#define HIPCHK(expr)                       \
+  do {                                     \
+    if ((expr) != hipSuccess) return EKF_E_HIP; \
+  } while (0)
+
+namespace ekfslam {
+
+// fn(float{}) or fn(double{}) by the handle's dtype
+template <typename Fn>
+auto by_dtype(const ekf_ctx* h, Fn fn) {
+  return h->cfg.dtype == EKF_F32 ? fn(float{}) : fn(double{});
+}
+
+// ---- ekf_sched.cpp ----
+constexpr int kCuSplitMaxFilters = 32;  // more filters: no CU split (create_streams)
+constexpr size_t kDescInit = 256;       // descriptors at creation (×F/64 for wide handles)
+int create_streams(ekf_ctx* h);         // both streams, their CU masks, devsync
+int am_route(ekf_ctx* h, bool joseph);  // which path unknown association takes (EKF_ASSOC_*)
+// the route in effect: the Joseph form keeps the chunk route only where its kernel fits alike
+inline int assoc_route(const ekf_ctx* h) {
+  return h->plan.joseph() && h->am_route_j != h->am_route ? EKF_ASSOC_MARKER : h->am_route;
+}
+int reserve_upload(ekf_ctx* h, size_t need);
+int init_diag(ekf_ctx* h, void* sig0, int nf);  // Σ₀ diagonal of nf filters from sig0 on
+int flush(ekf_ctx* h);                // upload the plan and enqueue its launches
+int submit(ekf_ctx* h);               // flush, unless deferred and the plan is still small
+bool plan_is_large(const ekf_ctx* h); // ≥ kFlushDesc descriptors planned
+int drain(ekf_ctx* h);                // both streams idle
+int adopt_device_plan(ekf_ctx* h);    // a device replay's planning state into the planner
+int settle(ekf_ctx* h);               // flush, drain, adopt: before any host access to device state
+int take_fatal(ekf_ctx* h);
+int take_numeric(ekf_ctx* h, int f, unsigned* fl_out);
+int status_rc(ekf_ctx* h, int f, bool range);
+// association with the decisions read back, for the message in the planner's slots [0, nf)
+int assoc_sync(ekf_ctx* h, int f0, int nf, bool predict, bool posterior, int m_max, int* j_out,
+               int* new_out);
+int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* d_ids,
+                  const int* d_actions, const double* d_rel_xy, const double* d_odom);
+
+}  // namespace ekfslam

@@ -1,5 +1,6 @@
 // Device-side data layout shared by the kernels (ekf_chain.hip, ekf_factors.hip, ekf_sigma_pass.hip,
-// ekf_assoc.hip, ekf_resident.hip) and the host runtime (ekf_api.cpp).
+// ekf_assoc.hip, ekf_resident.hip, plan_kernels.hip) and the host runtime (the planner ekf_plan.cpp,
+// the scheduler ekf_sched.cpp). Plain structs and constants: nothing of HIP is included.
 //
 // HBM layout per filter f (row-major, fp64 or fp32 per ekf_config.dtype):
 //   Σ[2]      : two n × ld ping-pong copies (ld = n rounded up to 128 bytes). One launch pair reads
@@ -126,5 +127,34 @@ struct alignas(16) AmCur {
   double kk[4], kp[6], pk[6], x[2], pad[2];
 };
 static_assert(sizeof(AmHist) == 96 && sizeof(AmCur) == 160, "AmHist / AmCur 16-byte rows");
+
+// ---- plans ----
+// What one launch of a plan runs (Launch::kind on the host, PlanEntry::kind and k_resident on the
+// device: the numerals travel in uploaded plans).
+enum LaunchKind : int {
+  kLaunchKnown = 0,       // gain + Σ pass of a known-association chunk
+  kLaunchAssoc = 1,       // association + gain + Σ pass, one marker (k_assoc)
+  kLaunchPosterior = 2,   // posterior only
+  kLaunchAssocChunk = 3,  // a chunk of associated markers (k_assoc_msg) + Σ pass
+};
+
+// Resident path (ekf_resident.hip): one plan entry = the descriptors desc[off + f − f0] of filters
+// [f0, f0 + nf); kind is a LaunchKind (kLaunchKnown, kLaunchAssoc or kLaunchPosterior).
+struct alignas(16) PlanEntry {
+  int off, f0, nf, kind;
+};
+
+// A filter's planning state between messages: the host planner's mirror (ekf_plan.hpp), and what a
+// known-association replay planned on the GPU (plan_kernels.hip, ekf_replay_device) reads before
+// and leaves after a replay.
+struct alignas(16) PlanState {
+  int parity;    // Σ / x copy that is "in"
+  int prev_m;    // markers of the filter's last pipelined chunk (−1: none, the next one gathers)
+  int pending;   // a predict is pending (folded into the next chunk)
+  int pad;
+  int prev_ids[kMaxChunk];
+  double odom[3];  // t_odom_robot of the last message
+  double pad2;
+};
 
 }  // namespace ekfslam

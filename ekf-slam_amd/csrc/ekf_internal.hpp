@@ -1,4 +1,4 @@
-// Runtime internals shared by the filter runtime (ekf_api.cpp) and the on-device simulator
+// Runtime internals shared by the filter runtime (ekf_sched.cpp) and the on-device simulator
 // (sim_api.cpp): how a device-written plan of known-association messages runs on a handle.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,7 +19,7 @@ struct HandleInfo {
 
 // Runs everything the host has planned so far (flush) and describes the handle.
 int handle_info(ekf_t h, HandleInfo* out);
-// The parity each filter's next chunk reads (host mirror).
+// The parity each filter's next chunk reads (the planner's mirror).
 int handle_parity(ekf_t h, int* parity);
 // T messages whose descriptors the device wrote into dd[t·F + f] on the handle's main stream (one
 // known-association chunk per message, the first of each filter non-pipelined), and for the

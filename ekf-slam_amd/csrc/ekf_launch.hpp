@@ -1,6 +1,6 @@
 // Kernel launchers (each defined beside its kernel: ekf_chain.hip, ekf_factors.hip,
 // ekf_sigma_pass.hip, ekf_assoc.hip, ekf_resident.hip, plan_kernels.hip, ekf_small.hip; called by
-// the host runtime in ekf_api.cpp).
+// the host scheduler in ekf_sched.cpp).
 // Optional e0/e1: timing events carried by the dispatch itself (kernel execution time).
 #pragma once
 #include <hip/hip_ext.h>
@@ -104,7 +104,7 @@ struct AmArgs {
 // Workgroups of k_assoc_msg one CU holds at once (its LDS bounds it), for the co-residency check:
 // a filter's G workgroups spin on each other, so all of them must fit the bulk stream's CUs
 // (per XCD in the XCD-local placement) at once, or the host routes the markers through the
-// one-marker-per-launch path instead (ekf_api.cpp am_route). joseph: the Joseph-form kernel (its
+// one-marker-per-launch path instead (ekf_sched.cpp am_route). joseph: the Joseph-form kernel (its
 // history rows are 96 bytes, so its LDS is larger).
 int assoc_msg_blocks_per_cu(bool f32, bool joseph);
 // Scores, decides and corrects every marker of the chunk (slam.cpp:338-488) and writes the chunk's
@@ -119,29 +119,16 @@ hipError_t launch_assoc_msg(const PassArgs<T>& a, const AmArgs& b, int n_filters
 template <typename T>
 hipError_t launch_posterior(const PassArgs<T>& a, int n_filters, hipStream_t s);
 
-// Resident path (ekf_resident.hip): n ≤ kResidentMaxN, fp64. One plan entry = the descriptors
-// desc[off + f − f0] of filters [f0, f0 + nf) (kind as ekf_api.cpp's Launch: 0 known chunk,
-// 1 association + correction, 2 posterior only). One 1024-thread workgroup per filter
-// [flo, flo + nfil) keeps Σ and x in registers across every entry of the plan.
+// Resident path (ekf_resident.hip): n ≤ kResidentMaxN, fp64. One 1024-thread workgroup per filter
+// [flo, flo + nfil) keeps Σ and x in registers across every entry of the plan (PlanEntry,
+// ekf_device.hpp).
 constexpr int kResidentMaxN = 128;
-struct alignas(16) PlanEntry {
-  int off, f0, nf, kind;
-};
 hipError_t launch_resident(const PassArgs<double>& a, const PlanEntry* plan, int nplan, int flo,
                            int nfil, hipStream_t s, hipEvent_t e0 = nullptr,
                            hipEvent_t e1 = nullptr);
 
-// Known-association replay planned on the GPU (plan_kernels.hip, ekf_replay_device): a filter's
-// planning state between messages — ekf_api.cpp's host mirror of it — before and after a replay.
-struct alignas(16) PlanState {
-  int parity;    // Σ / x copy that is "in"
-  int prev_m;    // markers of the filter's last pipelined chunk (−1: none, the next one gathers)
-  int pending;   // a predict is pending (folded into the next chunk)
-  int pad;
-  int prev_ids[kMaxChunk];
-  double odom[3];  // t_odom_robot of the last message
-  double pad2;
-};
+// Known-association replay planned on the GPU (plan_kernels.hip, ekf_replay_device): PlanState
+// (ekf_device.hpp) before and after a replay.
 struct ReplayArgs {
   const int* counts;      // [T][F]
   const int* ids;         // [T][F][M]

@@ -382,8 +382,8 @@ __global__ __launch_bounds__(W * 64) void k_resident(PassArgs<double> A, const P
       tmo[2] = ctl->tmo[2];
       counter = ctl->counter;
     }
-    if (post && L.kind != 2 && !(flags & kFirst)) posterior_now();  // corrections follow
-    if (L.kind != 2) {
+    if (post && L.kind != kLaunchPosterior && !(flags & kFirst)) posterior_now();  // corrections follow
+    if (L.kind != kLaunchPosterior) {
       if (flags & kFirst) {  // predict, slam.cpp:184-198: Σ = AΣAᵀ + Q̄, A = I + α·e0ᵀ
         b ^= 1;
         gather(b, -8, 0);
@@ -413,7 +413,7 @@ __global__ __launch_bounds__(W * 64) void k_resident(PassArgs<double> A, const P
         set_x(1, cur.x);
         set_x(2, cur.y);
       }
-      if (L.kind == 0) {  // known association, slam.cpp:201-271
+      if (L.kind == kLaunchKnown) {  // known association, slam.cpp:201-271
         for (int c = 0; c < d.m; ++c) {
           const int id = d.ids[c];
           if (id < 0 || id >= N) continue;  // validated on the host; never reached
@@ -547,7 +547,7 @@ __global__ __launch_bounds__(W * 64) void k_resident(PassArgs<double> A, const P
       par ^= 1;
       dirty = true;
     }
-    if ((flags & kLast) || L.kind == 2) {  // posterior, slam.cpp:273-291 (deferred)
+    if ((flags & kLast) || L.kind == kLaunchPosterior) {  // posterior, slam.cpp:273-291 (deferred)
       post = true;
       podom[0] = d.odom[0];
       podom[1] = d.odom[1];

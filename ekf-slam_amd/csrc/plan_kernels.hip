@@ -1,5 +1,5 @@
 // Known-association replay planned on the GPU (ekf_replay_device, include/ekf.h): for every
-// message t and filter f the MsgDesc that ekf_api.cpp's plan_known writes on the host for the
+// message t and filter f the MsgDesc that ekf_plan.cpp's Planner::known writes on the host for the
 // same inputs (one chunk per message, m ≤ kMaxChunk), built from inputs already in HBM.
 //
 // One wave per (t, f), all in parallel. What a host plan carries from chunk to chunk is found by
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(64) void k_plan_replay(ReplayArgs A) {
     if (lane < 3) d.odom[lane] = od;
     if (lane == 0) {
       int flags = kActive | kFirst | kLast | (A.joseph ? kJoseph : 0) | (prev_m >= 0 ? kLook : 0);
-      // the chain two chunks on rebuilds from operands this chunk's Σ pass stages (plan_known:
+      // the chain two chunks on rebuilds from operands this chunk's Σ pass stages (Planner::known:
       // both chunks in this plan); this chunk reads the ones staged two chunks back
       if (A.stage && prev_m >= 0 && prev2 >= 0) flags |= kStageIn;
       if (A.stage && next2 >= 0) {

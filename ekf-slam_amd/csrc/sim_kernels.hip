@@ -2,7 +2,7 @@
 // messages in order — nusim's slipping wheels and DiffDrive::FKin truth (nusim/src/nusim.cpp:222-230,
 // turtlelib/src/diff_drive.cpp:10-28) and the encoders' odometry (slam.cpp:599-634), the fake
 // sensor (nusim.cpp:317-346) over the map on all 64 lanes, then the message's descriptor for the
-// filter kernels (what ekf_api.cpp's plan_known writes on the host).
+// filter kernels (what ekf_plan.cpp's Planner::known writes on the host).
 //
 // FKin composes one arc per tick: config ← config · Δ_k. The ticks of a message are independent
 // until that product, so lane j integrates tick j's arc and the wave composes the arcs with an

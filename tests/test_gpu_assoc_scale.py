@@ -7,7 +7,7 @@ every decision equal to the oracle's, the state within the tolerances of tests/t
 
 Also: more filters than the GPU holds workgroups at once (64 filters × 16 = 1 024 workgroups:
 a filter's workgroups spin on each other, so the host launches them in groups the CUs hold at
-once, ekf_api.cpp assoc_msg_group), the one-marker-per-launch route when a filter's workgroups
+once, ekf_sched.cpp assoc_msg_group), the one-marker-per-launch route when a filter's workgroups
 cannot all be resident (EKF_CU_SPLIT leaves the bulk stream one CU per XCD), the single-stream
 schedule (EKF_SERIAL=1: the association runs on the main stream's narrower CU mask), and a forced
 exchange timeout, which must reach the caller as EKF_E_TIMEOUT / EKF_FLAG_TIMEOUT."""

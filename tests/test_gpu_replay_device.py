@@ -1,6 +1,6 @@
 """ekf_replay_device (include/ekf.h): a known-id replay whose inputs already live on the GPU, its
 descriptors planned by k_plan_replay (plan_kernels.hip). Parity: the same replay through the
-host planner (ekf_replay, plan_known in ekf_api.cpp) — the reference's fake_sensor_cb
+host planner (ekf_replay, Planner::known in ekf_plan.cpp) — the reference's fake_sensor_cb
 (nuslam/src/slam.cpp:180-316) message by message — and the CPU oracle."""
 import numpy as np
 import pytest
@@ -198,7 +198,7 @@ def test_joseph_handover_36_filters(monkeypatch, env):
 def test_posterior_then_device_replay(monkeypatch):
     """ekf_posterior enqueues k_posterior on the main stream, reading its descriptor in the upload
     buffer; with device epochs the next ekf_replay_device plans on the bulk stream and rewrites that
-    buffer, so it must wait for the posterior first (ekf_api.cpp main_unordered). Four filters:
+    buffer, so it must wait for the posterior first (ekf_sched.cpp main_unordered). Four filters:
     host span, a posterior per filter, device span — against the single-stream schedule (planner
     and posterior in one stream order): bit-identical state and t_map_odom."""
     scs = [synth.synthetic(80, 24, seed=31 + k) for k in range(4)]
@@ -293,7 +293,7 @@ def test_device_replay_rejects():
                          ids=["1filter", "4filters", "3filters_events", "2filters_serial"])
 def test_device_replay_joseph_equals_host(monkeypatch, F, env):
     """Joseph form (ekf_set_joseph) through the device planner: one kJoseph chunk per message
-    (plan_kernels.hip), as the host plans it (plan_known, kMaxJoseph = kMaxChunk). fp64 N = 96, up
+    (plan_kernels.hip), as the host plans it (Planner::known, kMaxJoseph = kMaxChunk). fp64 N = 96, up
     to 12 markers per message, holes (empty and all-DELETE messages): the two end alike, and filter
     0 equals the C oracle's Joseph mode."""
     for k in ("EKF_SERIAL", "EKF_CU_SPLIT", "EKF_DEVSYNC", "EKF_STAGE"):
