@@ -66,7 +66,11 @@ struct ChainSharedT {
   double row0raw[kMaxU];  // Σ_in[0][u_b]
   double col0raw[kMaxU];  // Σ_in[u_a][0]
   double xU[1][kMaxU];    // x[U], owned by wave 0 during the corrections
-  double P[1][kMaxU][kMaxU + 1];    // Σ[U,U] (rows all, columns live)
+  // im.D = Σ[U,U], the chain's block (rows all, columns live). kLook: im.R = Σ_pred'[U][U'] and
+  // im.C = Σ_pred'[U'][U] (U' = the previous chunk's index set; k over U' padded to 36 with zeros,
+  // so MFMA operand reads need no predicate). One struct with StageRec's payload: a staged image
+  // lands here piece by piece.
+  RebuildImage<double> im;
   double Cz[kMaxChunk][4];  // wave 1, step c: C_k = M_k[:, pA_c]·Hᵀ·S⁻¹ (2×2) for k < c
   double Dy[kMaxChunk][4];  // wave 2, step c: D_k = H·K_k[pA_c] (2×2) for k < c
   double KU[kMaxChunk][kMaxU][2];
@@ -92,8 +96,6 @@ struct ChainSharedT {
     // k (over U') padded to kMaxU + 1 = 36 with zeros, so MFMA operand reads need no predicate
     double Z[kMaxU + 1][ZC + 1];
     double Y[kZC][kMaxU + 1];
-    double R[kMaxU][kMaxU + 1];       // Σ_pred'[U][U']  (U' = previous chunk's index set)
-    double C[kMaxU + 1][kMaxU + 1];   // Σ_pred'[U'][U]
     double K[kMaxU][ZC + 1];      // R·Z'  = the previous K_c at U (Joseph: and V_c at U)
     double M[kZC][kMaxU + 1];     // Y'·C  = the previous M_c at U
     double r0U[kMaxU], c0U[kMaxU], r0P[kMaxU], c0P[kMaxU];
@@ -171,8 +173,8 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
 #pragma unroll
   for (int a = 0; a < 5; ++a) {
     const int col = a < 3 ? a : 3 + a - 3;  // pA of step 0 = {0, 1, 2, 3, 4}
-    pk[a] = sh.P[pb][lr][col];
-    pm[a] = sh.P[pb][col][lr];
+    pk[a] = sh.im.D[lr][col];
+    pm[a] = sh.im.D[col][lr];
   }
   // Look-ahead operands of the next marker's cross (see the step): rn = Σ[ℓ, nx..nx+1] and
   // qn = Σ[nx..nx+1, ℓ] one step old, and the previous step's K (kp) and M (mp) of this lane.
@@ -180,8 +182,8 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int col = min(5 + j, kMaxU - 1);
-    rn[j] = sh.P[pb][lr][col];
-    qn[j] = sh.P[pb][col][lr];
+    rn[j] = sh.im.D[lr][col];
+    qn[j] = sh.im.D[col][lr];
   }
   // A step's geometry (first sighting, ẑ, H) needs only x after the step before. It is computed
   // right after that step's state update, ahead of the step's cross update, so the two
@@ -330,8 +332,8 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        rn[j] = sh.P[pb][lr][nx + 2 + j];
-        qn[j] = sh.P[pb][nx + 2 + j][lr];
+        rn[j] = sh.im.D[lr][nx + 2 + j];
+        qn[j] = sh.im.D[nx + 2 + j][lr];
       }
     }
     const int jx = __builtin_amdgcn_readlane(ul, pj);  // sh.u[pj] (ul = sh.u[lane], pj < kMaxU)
@@ -416,7 +418,7 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
         const int col = k < 3 ? k : nx + k - 3;
         pk[k] = rank2_sub(xr[k], K0, K1, mx0[k], mx1[k]);
         if (J) pk[k] = rank2_sub(pk[k], V0, V1, kx0[k], kx1[k]);
-        *(lane < nu ? &sh.P[pb][lane][col] : &sh.junk[0][lane]) = pk[k];
+        *(lane < nu ? &sh.im.D[lane][col] : &sh.junk[0][lane]) = pk[k];
       }
       // Bx rows × every other column (the block is kept whole so that the chunk's final Σ[U,U]
       // can seed the next chunk): next step's pm there
@@ -427,7 +429,7 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
         double v = rank2_sub(xq[k], kx0[k], kx1[k], mm0, mm1);
         if (J) v = rank2_sub(v, vx0[k], vx1[k], K0, K1);
         pm[k] = v;
-        *(later ? &sh.P[pb][row][lane] : &sh.junk[0][lane]) = v;
+        *(later ? &sh.im.D[row][lane] : &sh.junk[0][lane]) = v;
       }
       // (the Bx × Bx entries: lane `row` stored the same value as its pk, same operands)
       kp0 = K0;
@@ -441,11 +443,12 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
   }
 }
 
-// The previous chunk's predict on the gathered rebuild operands: v + α_i·Σ[0][j] +
-// (Σ[i][0] + α_i·Σ00)·α_j + Q̄, for D = Σ_in'[U, U] → P, R = Σ_in'[U, U'] → pv.R and
-// C = Σ_in'[U', U] → pv.C (R / C columns k ≥ |U'| up to 36 zeroed: MFMA k padding). Thread tid's
-// entries e = tid + i·256 of the 36 × 36 block. Reads sh.u (U), sh.pv.u (U'), the staged row 0 /
-// column 0 (pv.r0U, c0U, r0P, c0P) and the previous predict (pv.first, a1, a2).
+// The previous chunk's predict on the rebuild operands: v + α_i·Σ[0][j] +
+// (Σ[i][0] + α_i·Σ00)·α_j + Q̄, for D = Σ_in'[U, U] → im.D, R = Σ_in'[U, U'] → im.R and
+// C = Σ_in'[U', U] → im.C (R / C columns k ≥ |U'| up to 36 zero: MFMA k padding). The raw blocks
+// are in LDS first — a staged image (k_patch_stage) copied in, or a gathering chain's own loads
+// (thread tid's entries e = tid + i·256 of the 36 × 36 block) — then predict_prev applies the
+// predict from the raw row 0 / column 0 (pv.r0U, c0U, r0P, c0P; pv.first, a1, a2).
 constexpr int kChainThreads = 256;
 constexpr int kRebW = kMaxU + 1;                                      // 36: entry e = a·36 + b
 constexpr int kRebPer = (kRebW * kRebW + kChainThreads - 1) / kChainThreads;  // 6
@@ -469,81 +472,52 @@ __device__ __forceinline__ void special_entry(int s, int& a, int& b) {
   }
 }
 
+// A gathering chain's raw blocks, stored at the image's positions with the image's zeros (what
+// k_patch_stage stores for a staged chain): thread tid's entries e = tid + 256·i = (a, b) of the
+// 36-wide blocks, C transposed.
 template <typename T, typename Shared>
-__device__ __forceinline__ void rebuild_rcd(Shared& sh, double (&P)[kMaxU][kMaxU + 1],
-                                            const T (&vd)[kRebPer], const T (&vr)[kRebPer],
-                                            const T (&vc)[kRebPer], int tid, int nu, int np,
-                                            double q) {
-  constexpr int kW = kRebW, kPer = kRebPer;
-  // the raw blocks: no LDS read
+__device__ __forceinline__ void store_raw_image(Shared& sh, const T (&vd)[kRebPer],
+                                                const T (&vr)[kRebPer], const T (&vc)[kRebPer],
+                                                int tid, int nu, int np) {
 #pragma unroll
-  for (int i = 0; i < kPer; ++i) {
+  for (int i = 0; i < kRebPer; ++i) {
     const int e = tid + i * kChainThreads;
-    const int a = e / kW, b = e % kW;
-    if (a < nu && b < nu) P[a][b] = static_cast<double>(vd[i]);
-    if (a < nu) {  // b = k over U' (36: the MFMA k padding, zero)
-      sh.pv.R[a][b] = b < np ? static_cast<double>(vr[i]) : 0.0;
-      sh.pv.C[b][a] = b < np ? static_cast<double>(vc[i]) : 0.0;
+    const int a = e / kRebW, b = e % kRebW;
+    if (a < kMaxU) {
+      sh.im.D[a][b] = a < nu && b < nu ? static_cast<double>(vd[i]) : 0.0;
+      sh.im.R[a][b] = a < nu && b < np ? static_cast<double>(vr[i]) : 0.0;
     }
+    if (e < kRebW * kRebW) sh.im.C[b][a] = a < nu && b < np ? static_cast<double>(vc[i]) : 0.0;
   }
+}
+
+// The previous chunk's predict over the raw image in LDS (staged or gathered: the one body both
+// paths run), one special entry (a, b) per thread applied to D, R and C. An entry depends only on
+// its own raw value and the raw row 0 / column 0 (pv.r0U, c0U, r0P, c0P), so one wait covers
+// every operand read and no barrier separates reads from writes.
+template <typename Shared>
+__device__ __forceinline__ void predict_prev(Shared& sh, int tid, int nu, int np, double q) {
   if (sh.pv.first == 0) return;  // (uniform)
-  // The previous predict on the special entries, by the thread that gathered them (its raw values
-  // are in registers, so no barrier): a thread's entries e = tid + 256·i have b = (tid % 36 + 4·i)
-  // mod 36, so besides position 0 (rows 1, 2 are e ∈ [36, 108); (0, 0) is e = 0) at most one
-  // position ic ≥ 1 falls in column 1 or 2. Both are rewritten over the raw stores above (same
-  // thread, same address: LDS order), with one wait for all operand reads and no branch.
-  const int r = tid % kW;
-  int ic = 0;
-#pragma unroll
-  for (int i = 1; i < kPer; ++i) {
-    const int bb = (r + 4 * i) % kW;
-    ic = (bb == 1 || bb == 2) && tid + i * kChainThreads < kW * kW ? i : ic;
-  }
-  double sv[2][3];
-  sv[0][0] = static_cast<double>(vd[0]);
-  sv[0][1] = static_cast<double>(vr[0]);
-  sv[0][2] = static_cast<double>(vc[0]);
-  sv[1][0] = sv[1][1] = sv[1][2] = 0.0;
-#pragma unroll
-  for (int i = 1; i < kPer; ++i) {
-    sv[1][0] = ic == i ? static_cast<double>(vd[i]) : sv[1][0];
-    sv[1][1] = ic == i ? static_cast<double>(vr[i]) : sv[1][1];
-    sv[1][2] = ic == i ? static_cast<double>(vc[i]) : sv[1][2];
-  }
+  int a, b;
+  special_entry(min(tid, kSpec - 1), a, b);
+  const bool sp = tid < kSpec;
+  const int ac = min(a, kMaxU - 1), bc = min(b, kMaxU - 1);
   const double s00 = sh.pv.r0U[0], qa1 = sh.pv.a1, qa2 = sh.pv.a2;
-  int pa[2], pb[2];
-  bool sp[2];
-  double r0u_b[2], c0u_a[2], r0p_b[2], r0u_a[2], c0p_b[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int e = tid + (j ? ic : 0) * kChainThreads;
-    const int a = e / kW, b = e % kW;
-    pa[j] = a;
-    pb[j] = b;
-    sp[j] = j ? ic > 0 : (a == 1 || a == 2 || b == 1 || b == 2 || e == 0);
-    const int ac = min(a, kMaxU - 1), bc = min(b, kMaxU - 1);
-    r0u_b[j] = sh.pv.r0U[bc];
-    c0u_a[j] = sh.pv.c0U[ac];
-    r0p_b[j] = sh.pv.r0P[bc];
-    r0u_a[j] = sh.pv.r0U[ac];
-    c0p_b[j] = sh.pv.c0P[bc];
-  }
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int a = pa[j], b = pb[j];
-    const double ai = alpha_of(a, qa1, qa2), aj = alpha_of(b, qa1, qa2);
-    const bool qd = a == b && a < 3;
-    double v = sv[j][0] + ai * r0u_b[j];  // D = Σ_in'[U, U] → P
-    v = v + (c0u_a[j] + ai * s00) * aj;
-    double v2 = sv[j][1] + ai * r0p_b[j];  // R = Σ_in'[U, U'] (b = k over U')
-    v2 = v2 + (c0u_a[j] + ai * s00) * aj;
-    double w2 = sv[j][2] + aj * r0u_a[j];  // C = Σ_in'[U', U]
-    w2 = w2 + (c0p_b[j] + aj * s00) * ai;
-    const bool okd = sp[j] && a < nu && b < nu, okr = sp[j] && a < nu && b < np;
-    *(okd ? &P[a][b] : &sh.junk[0][tid & 63]) = qd ? v + q : v;
-    *(okr ? &sh.pv.R[a][b] : &sh.junk[1][tid & 63]) = qd ? v2 + q : v2;
-    *(okr ? &sh.pv.C[b][a] : &sh.junk[2][tid & 63]) = qd ? w2 + q : w2;
-  }
+  const double rd = sh.im.D[ac][b], rr = sh.im.R[ac][b], rc = sh.im.C[b][ac];
+  const double r0u_b = sh.pv.r0U[bc], c0u_a = sh.pv.c0U[ac], r0p_b = sh.pv.r0P[bc];
+  const double r0u_a = sh.pv.r0U[ac], c0p_b = sh.pv.c0P[bc];
+  const double ai = alpha_of(a, qa1, qa2), aj = alpha_of(b, qa1, qa2);
+  const bool qd = a == b && a < 3;
+  double v = rd + ai * r0u_b;  // D = Σ_in'[U, U]
+  v = v + (c0u_a + ai * s00) * aj;
+  double v2 = rr + ai * r0p_b;  // R = Σ_in'[U, U'] (b = k over U')
+  v2 = v2 + (c0u_a + ai * s00) * aj;
+  double w2 = rc + aj * r0u_a;  // C = Σ_in'[U', U]
+  w2 = w2 + (c0p_b + aj * s00) * ai;
+  const bool okd = sp && a < nu && b < nu, okr = sp && a < nu && b < np;
+  *(okd ? &sh.im.D[ac][b] : &sh.junk[0][tid & 63]) = qd ? v + q : v;
+  *(okr ? &sh.im.R[ac][b] : &sh.junk[1][tid & 63]) = qd ? v2 + q : v2;
+  *(okr ? &sh.im.C[b][ac] : &sh.junk[2][tid & 63]) = qd ? w2 + q : w2;
 }
 
 // One workgroup per filter, persistent over the `nchunks` chunks of a launch (descriptors
@@ -594,7 +568,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
   }
   pre = false;
   const MsgDesc& d = sdesc[ci & 1];
-  auto& P = sh.P[0];
+  auto& P = sh.im.D;
   const bool active = (d.flags & kActive) != 0;
   const bool look = (d.flags & kLook) != 0 && !A.gather;
   // Publish the previous chunk's record before this chunk waits on anything the bulk stream
@@ -644,51 +618,68 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
 
   constexpr int kW = kMaxU + 1;  // block entries are indexed e = a·36 + b (constant divisor)
   constexpr int kPer = (kW * kW + kChainThreads - 1) / kChainThreads;  // 6
-  // the previous record's Z (|U| rows of ZC, the record's rows kZJ wide) and Y (kZC rows)
-  constexpr int kPerZ = (kMaxU * ZC + kChainThreads - 1) / kChainThreads;  // 5 (Joseph: 9)
+  // Everything below comes in as 16-byte pieces (one buffer_load_dwordx4 each). The staged image
+  // (StageRec::im) has the LDS image's element order, so piece p goes to piece p of sh.im; the
+  // previous record's Z (|U| rows of ZC, the record's rows kZJ wide: ZC / 2 pieces a row) and Y
+  // (kZC × kMaxU contiguous) are pairs of neighbours.
+  constexpr int kImPieces = static_cast<int>(sizeof(RebuildImage<T>) / 16);  // 954 (fp32) / 1 908
+  constexpr int kPerIm = (kImPieces + kChainThreads - 1) / kChainThreads;    // 4 / 8
+  constexpr int kZP = ZC / 2, kZPieces = kMaxU * kZP;                        // 560 (Joseph: 1 120)
+  constexpr int kPerZ = (kZPieces + kChainThreads - 1) / kChainThreads;      // 3 (Joseph: 5)
+  constexpr int kYPieces = kZC * kMaxU / 2;                                  // 560
+  constexpr int kPerY = (kYPieces + kChainThreads - 1) / kChainThreads;      // 3
+  static_assert(sizeof(sh.im) == 2 * sizeof(RebuildImage<float>) && alignof(decltype(sh.im)) >= 16 &&
+                    (kZC * kMaxU) % 2 == 0 && ZC % 2 == 0,
+                "the staged image and the record's Z / Y are copied in 16-byte pieces");
   // kLook with staged operands: the loads do not depend on A0's index sets, so they are issued
   // here and land during A0 (whose barrier orders LDS only)
   const bool early = look && (d.flags & kStageIn);
-  double vz[kPerZ], vy[kPer];
-  T vd[kPer], vr[kPer], vc[kPer];  // (as stored: half the registers at fp32 while A0 runs)
+  q16 vim[kPerIm], vz[kPerZ], vy[kPerY];
   double r0u = 0.0, c0u = 0.0, r0p = 0.0, c0p = 0.0, x2 = 0.0;
   double x0 = 0.0, x1 = 0.0, pa1 = 0.0, pa2 = 0.0, tq = 0.0;
   int pflags = 0;
-  {
-    // staged by the k_patch_stage two chunks back, right behind the Σ pass that wrote Σ_in':
-    // the same values as the gather below, contiguous (≈ 5 000 cycles less than the ≈ 1 900
-    // scattered lines of the gather through one CU). Issued unconditionally, through buffer
-    // descriptors of size 0 unless `early` (zeros, no access): a load under a branch is waited for
-    // at the branch's join on the path that skipped it — vmcnt(0) before A0's first use of `aj`
-    const int tc = tid < kMaxU ? tid : 0;
-    const StageRec<T>* sg = A.stage + static_cast<size_t>(d.parity) * A.rec_stride + f;
-    const auto rs = buf_rsrc(sg, early ? static_cast<unsigned>(sizeof(StageRec<T>)) : 0u);
-    const auto rr = buf_rsrc(rp, early ? static_cast<unsigned>(sizeof(ChunkRec)) : 0u);
+  // the previous record: Z', Y', x[U'], Zx' and its predict (through a descriptor: size 0 = zeros)
+  auto load_rec = [&](__amdgpu_buffer_rsrc_t rr) {
     constexpr unsigned oZ = offsetof(ChunkRec, Z), oY = offsetof(ChunkRec, Y);
-    constexpr unsigned oV = offsetof(StageRec<T>, v), oT = kW * kW * sizeof(T);
+    const int tc = tid < kMaxU ? tid : 0;
 #pragma unroll
     for (int i = 0; i < kPerZ; ++i) {
-      const int e = tid + i * kChainThreads, ez = e < kMaxU * ZC ? e : 0;
-      vz[i] = ld_f64(rr, oZ + 8u * ((ez / ZC) * kZJ + ez % ZC), 0);
+      const int p = tid + i * kChainThreads, pz = p < kZPieces ? p : 0;
+      vz[i] = ld_q16(rr, oZ + 8u * ((pz / kZP) * kZJ + 2 * (pz % kZP)));
     }
 #pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = tid + i * kChainThreads, es = min(e, kW * kW - 1);
-      vy[i] = ld_f64(rr, oY + 8u * (e < kZC * kMaxU ? e : 0), 0);
-      vd[i] = ld_t(rs, oV + sizeof(T) * es, T{});
-      vr[i] = ld_t(rs, oV + oT + sizeof(T) * es, T{});
-      vc[i] = ld_t(rs, oV + 2 * oT + sizeof(T) * es, T{});
+    for (int i = 0; i < kPerY; ++i) {
+      const int p = tid + i * kChainThreads;
+      vy[i] = ld_q16(rr, oY + 16u * (p < kYPieces ? p : 0));
     }
-    r0u = ld_f64(rs, offsetof(StageRec<T>, r0u) + 8u * tc, 0);
-    c0u = ld_f64(rs, offsetof(StageRec<T>, c0u) + 8u * tc, 0);
-    r0p = ld_f64(rs, offsetof(StageRec<T>, r0p) + 8u * tc, 0);
-    c0p = ld_f64(rs, offsetof(StageRec<T>, c0p) + 8u * tc, 0);
-    x2 = ld_f64(rs, offsetof(StageRec<T>, xg) + 8u * tc, 0);
     x0 = ld_f64(rr, offsetof(ChunkRec, xU) + 8u * tc, 0);
     x1 = ld_f64(rr, offsetof(ChunkRec, Zx) + 8u * tc, 0);
     pflags = static_cast<int>(__builtin_amdgcn_raw_buffer_load_b32(rr, offsetof(ChunkRec, flags), 0, 0));
     pa1 = ld_f64(rr, offsetof(ChunkRec, a1), 0);
     pa2 = ld_f64(rr, offsetof(ChunkRec, a2), 0);
+  };
+  {
+    // staged by the k_patch_stage two chunks back, right behind the Σ pass that wrote Σ_in':
+    // the same values as the gather below, in the LDS image's layout (≈ 5 000 cycles less than
+    // the ≈ 1 900 scattered lines of the gather through one CU). Issued unconditionally, through
+    // buffer descriptors of size 0 unless `early` (zeros, no access): a load under a branch is
+    // waited for at the branch's join on the path that skipped it — vmcnt(0) before A0's first use
+    // of `aj`
+    const int tc = tid < kMaxU ? tid : 0;
+    const StageRec<T>* sg = A.stage + static_cast<size_t>(d.parity) * A.rec_stride + f;
+    const auto rs = buf_rsrc(sg, early ? static_cast<unsigned>(sizeof(StageRec<T>)) : 0u);
+    constexpr unsigned oIm = offsetof(StageRec<T>, im);
+#pragma unroll
+    for (int i = 0; i < kPerIm; ++i) {
+      const int p = tid + i * kChainThreads;
+      vim[i] = ld_q16(rs, oIm + 16u * (p < kImPieces ? p : 0));
+    }
+    load_rec(buf_rsrc(rp, early ? static_cast<unsigned>(sizeof(ChunkRec)) : 0u));
+    r0u = ld_f64(rs, offsetof(StageRec<T>, r0u) + 8u * tc, 0);
+    c0u = ld_f64(rs, offsetof(StageRec<T>, c0u) + 8u * tc, 0);
+    r0p = ld_f64(rs, offsetof(StageRec<T>, r0p) + 8u * tc, 0);
+    c0p = ld_f64(rs, offsetof(StageRec<T>, c0p) + 8u * tc, 0);
+    x2 = ld_f64(rs, offsetof(StageRec<T>, xg) + 8u * tc, 0);
     tq = ctl->tmo[tid < 3 ? tid : 0];
   }
 
@@ -741,16 +732,12 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     const double* xp = A.x[d.parity ^ 1] + f * A.x_stride;
     const int np = sh.pv.nu;
     const int tc = tid < kMaxU ? tid : 0;
-    if (!early) {  // (early: the staged operands and the record's values are in registers)
-#pragma unroll
-      for (int i = 0; i < kPerZ; ++i) {
-        const int e = tid + i * kChainThreads, ez = e < kMaxU * ZC ? e : 0;
-        vz[i] = rp->Z[ez / ZC][ez % ZC];
-      }
+    if (!early) {  // (early: the staged image and the record's values are in registers)
+      load_rec(buf_rsrc(rp, static_cast<unsigned>(sizeof(ChunkRec))));
+      T vd[kPer], vr[kPer], vc[kPer];
 #pragma unroll
       for (int i = 0; i < kPer; ++i) {
         const int e = tid + i * kChainThreads;
-        vy[i] = (&rp->Y[0][0])[e < kZC * kMaxU ? e : 0];
         const int a = min(e / kW, kMaxU - 1), b = min(e % kW, kMaxU - 1);  // clamped: in bounds
         const size_t ua = static_cast<size_t>(sh.u[a]) * ld, pa = static_cast<size_t>(sh.pv.u[b]);
         vd[i] = Sp[ua + sh.u[b]];
@@ -764,23 +751,44 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
       r0p = static_cast<double>(Sp[pu]);
       c0p = static_cast<double>(Sp[static_cast<size_t>(pu) * ld]);
       x2 = xp[uu];
-      // record scalars
-      x0 = rp->xU[tc];
-      x1 = rp->Zx[tc];
-      pflags = rp->flags;
-      pa1 = rp->a1;
-      pa2 = rp->a2;
       tq = ctl->tmo[tid < 3 ? tid : 0];
+      // the raw gather at the image's positions (what a staged chain's image holds)
+      store_raw_image<T>(sh, vd, vr, vc, tid, nu, np);
+    } else {
+      // the staged image, piece p → piece p of sh.im (fp32: four values widened to two pieces)
+      d2m* const im = reinterpret_cast<d2m*>(&sh.im);
+#pragma unroll
+      for (int i = 0; i < kPerIm; ++i) {
+        const int p = tid + i * kChainThreads;
+        if (p < kImPieces) {
+          if constexpr (sizeof(T) == 8) {
+            im[p] = __builtin_bit_cast(d2m, vim[i]);
+          } else {
+            const f4v w = __builtin_bit_cast(f4v, vim[i]);
+            im[2 * p] = d2m{static_cast<double>(w.x), static_cast<double>(w.y)};
+            im[2 * p + 1] = d2m{static_cast<double>(w.z), static_cast<double>(w.w)};
+          }
+        }
+      }
     }
 #pragma unroll
     for (int i = 0; i < kPerZ; ++i) {
-      const int e = tid + i * kChainThreads;
-      if (e < kMaxU * ZC) (&sh.pv.Z[0][0])[(e / ZC) * (ZC + 1) + e % ZC] = vz[i];
+      const int p = tid + i * kChainThreads;
+      const d2m w = __builtin_bit_cast(d2m, vz[i]);
+      if (p < kZPieces) {
+        double* z = &sh.pv.Z[p / kZP][2 * (p % kZP)];
+        z[0] = w.x;
+        z[1] = w.y;
+      }
     }
 #pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = tid + i * kChainThreads;
-      if (e < kZC * kMaxU) (&sh.pv.Y[0][0])[(e / kMaxU) * (kMaxU + 1) + e % kMaxU] = vy[i];
+    for (int i = 0; i < kPerY; ++i) {
+      const int p = tid + i * kChainThreads, e0 = 2 * p, e1 = 2 * p + 1;
+      const d2m w = __builtin_bit_cast(d2m, vy[i]);
+      if (p < kYPieces) {
+        sh.pv.Y[e0 / kMaxU][e0 % kMaxU] = w.x;
+        sh.pv.Y[e1 / kMaxU][e1 % kMaxU] = w.y;
+      }
     }
     if (tid < ZC) sh.pv.Z[kMaxU][tid] = 0.0;  // the 36th k row / column
     if (tid < kZC) sh.pv.Y[tid][kMaxU] = 0.0;
@@ -802,8 +810,9 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     if (tid < 3) sh.tmo[tid] = tq;
     __syncthreads();
     EKF_STAMP(21);
-    rebuild_rcd<T>(sh, P, vd, vr, vc, tid, nu, np, A.q);
+    predict_prev(sh, tid, nu, np, A.q);
     __syncthreads();
+
     EKF_STAMP(3);
     EKF_STAMP(4);
     // K' = R·Z' (35 × 32) and M' = Y'·C (32 × 35) on f64 MFMA. Their 32 × 32 cores are 8 tiles,
@@ -824,8 +833,8 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
         const int ti = (kt ? tt : tt - 4) >> 1, tj = (kt ? tt : tt - 4) & 1;
         // A: R[row][k] (K') or Y'[row][k] (M'), k contiguous; B: Z'[k][col] (stride kZC + 1) or
         // C[k][col] (stride kMaxU + 1)
-        const double* pa = kt ? &sh.pv.R[16 * ti + i16][0] : &sh.pv.Y[16 * ti + i16][0];
-        const double* pb = kt ? &sh.pv.Z[0][16 * tj + i16] : &sh.pv.C[0][16 * tj + i16];
+        const double* pa = kt ? &sh.im.R[16 * ti + i16][0] : &sh.pv.Y[16 * ti + i16][0];
+        const double* pb = kt ? &sh.pv.Z[0][16 * tj + i16] : &sh.im.C[0][16 * tj + i16];
         const int sb = kt ? kZC + 1 : kMaxU + 1;
 #pragma unroll
         for (int s0 = 0; s0 < 9; ++s0) {
@@ -848,8 +857,8 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
           brow = u / 3;
           bcol = 32 + (u - 3 * (u / 3));
         }
-        const double* ra = bk ? &sh.pv.R[min(brow, kMaxU - 1)][0] : &sh.pv.Y[brow][0];
-        const double* cb = bk ? &sh.pv.Z[0][bcol] : &sh.pv.C[0][min(bcol, kMaxU)];
+        const double* ra = bk ? &sh.im.R[min(brow, kMaxU - 1)][0] : &sh.pv.Y[brow][0];
+        const double* cb = bk ? &sh.pv.Z[0][bcol] : &sh.im.C[0][min(bcol, kMaxU)];
         const int sc = bk ? kZC + 1 : kMaxU + 1;
 #pragma unroll
         for (int k = 0; k < kMaxU + 1; ++k) bacc[k & 3] = fma(ra[k], cb[k * sc], bacc[k & 3]);
@@ -861,7 +870,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
 #pragma unroll
         for (int k = kMaxU - 1; k >= 0; --k) pos = (k < np && sh.pv.u[k] == u) ? k : pos;
 #pragma unroll
-        for (int k = 0; k < kMaxU; ++k) bacc[k & 3] = fma(sh.pv.R[l][k], sh.pv.Zx[k], bacc[k & 3]);
+        for (int k = 0; k < kMaxU; ++k) bacc[k & 3] = fma(sh.im.R[l][k], sh.pv.Zx[k], bacc[k & 3]);
         const double r = (bacc[0] + bacc[1]) + (bacc[2] + bacc[3]);  // R[·][k ≥ |U'|] = 0
         xres = pos >= 0 ? sh.pv.xU[pos] : sh.pv.xg[l] + r;
       }
@@ -946,8 +955,8 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
         const int tt = wv + 4 * q;  // 0..7 K' tiles (2 × 4), 8..11 M' tiles (2 × 2)
         const bool kt = tt < 8;
         const int ti = kt ? tt >> 2 : (tt - 8) >> 1, tj = kt ? tt & 3 : (tt - 8) & 1;
-        const double* pa = kt ? &sh.pv.R[16 * ti + i16][0] : &sh.pv.Y[16 * ti + i16][0];
-        const double* pb = kt ? &sh.pv.Z[0][16 * tj + i16] : &sh.pv.C[0][16 * tj + i16];
+        const double* pa = kt ? &sh.im.R[16 * ti + i16][0] : &sh.pv.Y[16 * ti + i16][0];
+        const double* pb = kt ? &sh.pv.Z[0][16 * tj + i16] : &sh.im.C[0][16 * tj + i16];
         const int sb = kt ? ZC + 1 : kMaxU + 1;
         double av[9], bv[9];
 #pragma unroll
@@ -970,8 +979,8 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
           const bool bk = t < 192;  // K'[32 + t/64][t%64] = R[row]·Z'[:, col], else M'[u/3][32 + u%3]
           const int u = t - 192;
           const int brow = bk ? 32 + (t >> 6) : u / 3, bcol = bk ? (t & 63) : 32 + u % 3;
-          const double* ra = bk ? &sh.pv.R[min(brow, kMaxU - 1)][0] : &sh.pv.Y[brow][0];
-          const double* cb = bk ? &sh.pv.Z[0][bcol] : &sh.pv.C[0][min(bcol, kMaxU)];
+          const double* ra = bk ? &sh.im.R[min(brow, kMaxU - 1)][0] : &sh.pv.Y[brow][0];
+          const double* cb = bk ? &sh.pv.Z[0][bcol] : &sh.im.C[0][min(bcol, kMaxU)];
           const int sc = bk ? ZC + 1 : kMaxU + 1;
           double bacc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -989,7 +998,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
         for (int k = kMaxU - 1; k >= 0; --k) pos = (k < np && sh.pv.u[k] == u) ? k : pos;
         double bacc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int k = 0; k < kMaxU; ++k) bacc[k & 3] = fma(sh.pv.R[l][k], sh.pv.Zx[k], bacc[k & 3]);
+        for (int k = 0; k < kMaxU; ++k) bacc[k & 3] = fma(sh.im.R[l][k], sh.pv.Zx[k], bacc[k & 3]);
         const double r = (bacc[0] + bacc[1]) + (bacc[2] + bacc[3]);  // R[·][k ≥ |U'|] = 0
         const double xres = pos >= 0 ? sh.pv.xU[pos] : sh.pv.xg[l] + r;
         if (ln < nu) sh.xU[0][ln] = xres;

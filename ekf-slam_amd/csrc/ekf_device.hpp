@@ -102,15 +102,33 @@ static_assert(offsetof(ChunkRec, Z) % 16 == 0 && offsetof(ChunkRec, Y) % 16 == 0
 // The rebuild operands of a kLook chain (k_chain's prologue), gathered off the chain's path by the
 // k_patch_stage of the chunk two back, right behind the Σ pass that wrote them: with U this chunk's
 // index set and U' the previous chunk's, Σ = Σ_in' (the previous chunk's Σ_in), x = x_in',
-//   v[0][e] = Σ[u_a][u_b], v[1][e] = Σ[u_a][u'_b], v[2][e] = Σ[u'_b][u_a]   (a, b clamped to kMaxU−1)
+//   im.D[a][b] = Σ[u_a][u_b], im.R[a][k] = Σ[u_a][u'_k], im.C[k][a] = Σ[u'_k][u_a]
 //   r0u[t] = Σ[0][u_t], c0u[t] = Σ[u_t][0], r0p[t] = Σ[0][u'_t], c0p[t] = Σ[u'_t][0], xg[t] = x[u_t]
-// — the very values the chain would gather (the fp32 block patch included), stored contiguously.
-// [2][F] by the chain's Σ parity.
+// — the very values the chain would gather (the fp32 block patch included). [2][F] by the chain's
+// Σ parity.
+//
+// RebuildImage is the three blocks in the order, stride and padding of the chain's LDS arrays
+// (ChainSharedT::im is a RebuildImage<double>): element i of the staged image goes to element i of
+// the LDS image, so the chain copies it in 16-byte pieces with no per-entry index math. Zeros
+// where the chain's MFMA operands need them and in every slot the chain does not use: a ≥ |U|,
+// b ≥ |U| (D), k ≥ |U'| (R, C), the 36th column of every row and C's 36th row.
+template <typename E>
+struct alignas(16) RebuildImage {
+  E R[kMaxU][kStW];  // Σ_pred'[U][U']  (k over U' padded to 36: MFMA k padding)
+  E C[kStW][kStW];   // Σ_pred'[U'][U], transposed in place: C[k][a]
+  E D[kMaxU][kStW];  // Σ[U, U]: the chain's block
+};
 template <typename T>
 struct alignas(16) StageRec {
   double r0u[kStW], c0u[kStW], r0p[kStW], c0p[kStW], xg[kStW];
-  T v[3][kStW * kStW];
+  RebuildImage<T> im;
 };
+static_assert(sizeof(RebuildImage<float>) % 16 == 0 && sizeof(RebuildImage<double>) % 16 == 0 &&
+                  sizeof(RebuildImage<double>) == 2 * sizeof(RebuildImage<float>),
+              "RebuildImage copied in 16-byte pieces, the same element order at either width");
+static_assert(offsetof(StageRec<float>, im) % 16 == 0 && offsetof(StageRec<double>, im) % 16 == 0 &&
+                  sizeof(StageRec<float>) % 16 == 0 && sizeof(StageRec<double>) % 16 == 0,
+              "StageRec image 16-byte aligned");
 
 // ---- unknown association of a whole chunk in one launch (k_assoc_msg, ekf_assoc.hip) ----
 constexpr int kAmSlots = 64;  // landmark slots per workgroup: one wave, one slot per lane

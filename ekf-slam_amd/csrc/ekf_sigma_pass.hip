@@ -553,15 +553,24 @@ __global__ __launch_bounds__(256) void k_patch_stage(PassArgs<T> A) {
     const T g = S[static_cast<size_t>(r) * A.ld + c];
     return (patch && fr >= 0 && fc >= 0) ? static_cast<T>(spend[fr][fc]) : g;
   };
+  // The three blocks by image position (RebuildImage: the chain's LDS layout), entry e = row·36 +
+  // column of each: D and R rows a over U, C rows k over U' with a along the row (the transposed
+  // store the chain did). Loads unconditional (clamped), zeros selected after: a ≥ |U|, b ≥ |U|,
+  // k ≥ |U'| and the padding slots.
   constexpr int kSPer = (kStW * kStW + 255) / 256;  // 6
+  const int gnu = 3 + 2 * min(d.stg_m, kMaxChunk), gnp = 3 + 2 * min(d.stg_pm, kMaxChunk);
   T od[kSPer], orr[kSPer], oc[kSPer];
 #pragma unroll
   for (int i = 0; i < kSPer; ++i) {
     const int e = min(tid + 256 * i, kStW * kStW - 1);
-    const int a = min(e / kStW, kMaxU - 1), b = min(e % kStW, kMaxU - 1);
-    od[i] = val(sgu[a], sgfu[a], sgu[b], sgfu[b]);
-    orr[i] = val(sgu[a], sgfu[a], sgp[b], sgfp[b]);
-    oc[i] = val(sgp[b], sgfp[b], sgu[a], sgfu[a]);
+    const int r = e / kStW, c = e % kStW;
+    const int a = min(r, kMaxU - 1), b = min(c, kMaxU - 1);
+    const T vd = val(sgu[a], sgfu[a], sgu[b], sgfu[b]);
+    const T vr = val(sgu[a], sgfu[a], sgp[b], sgfp[b]);
+    const T vc = val(sgp[a], sgfp[a], sgu[b], sgfu[b]);  // C[k = r][a = c]
+    od[i] = r < gnu && c < gnu ? vd : T(0);
+    orr[i] = r < gnu && c < gnp ? vr : T(0);
+    oc[i] = r < gnp && c < gnu ? vc : T(0);
   }
   const int t = min(tid, kMaxU - 1);
   const int z = sgfu[0];  // position 0 of U is the pose θ column
@@ -578,11 +587,11 @@ __global__ __launch_bounds__(256) void k_patch_stage(PassArgs<T> A) {
 #pragma unroll
   for (int i = 0; i < kSPer; ++i) {
     const int e = tid + 256 * i;
-    if (e < kStW * kStW) {
-      sg->v[0][e] = od[i];
-      sg->v[1][e] = orr[i];
-      sg->v[2][e] = oc[i];
+    if (e < kMaxU * kStW) {
+      (&sg->im.D[0][0])[e] = od[i];
+      (&sg->im.R[0][0])[e] = orr[i];
     }
+    if (e < kStW * kStW) (&sg->im.C[0][0])[e] = oc[i];
   }
 }
 

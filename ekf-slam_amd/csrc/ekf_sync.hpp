@@ -77,6 +77,15 @@ typedef unsigned u2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double ld_f64(__amdgpu_buffer_rsrc_t r, unsigned vo, unsigned so) {
   return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
 }
+// A 16-byte piece (buffer_load_dwordx4) and its views as two doubles / four floats; d2m also as
+// the type of 16-byte LDS accesses to arrays of double (ds_read / ds_write_b128)
+typedef unsigned q16 __attribute__((ext_vector_type(4)));
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef double d2v_ __attribute__((ext_vector_type(2)));
+typedef d2v_ d2m __attribute__((may_alias));
+__device__ __forceinline__ q16 ld_q16(__amdgpu_buffer_rsrc_t r, unsigned vo) {
+  return __builtin_bit_cast(q16, __builtin_amdgcn_raw_buffer_load_b128(r, vo, 0, 0));
+}
 __device__ __forceinline__ float ld_t(__amdgpu_buffer_rsrc_t r, unsigned vo, float) {
   return ld_f32(r, vo, 0);
 }
