@@ -182,6 +182,9 @@ int ekf_destroy(ekf_t h) {
   for (PlanState* p : h->dstate)
     if (p) hipFree(p);
   if (h->hstate) hipHostFree(h->hstate);
+  if (h->odom_d) hipFree(h->odom_d);
+  if (h->odom_h) hipHostFree(h->odom_h);
+  if (h->ev_odom) hipEventDestroy(h->ev_odom);
   if (h->fatal_h) hipHostFree(h->fatal_h);
   if (h->am.hist) hipFree(h->am.hist);
   if (h->am.cur) hipFree(h->am.cur);
@@ -310,6 +313,28 @@ int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int*
   if (h->resident) return EKF_E_ARG;
   if (T == 0) return EKF_OK;
   return replay_device(h, T, m_max, d_counts, d_ids, d_actions, d_rel_xy, d_odom);
+}
+
+int ekf_replay_device_assoc(ekf_t h, int T, int m_max, const int* d_counts, const double* d_xy,
+                            int xy_stride, const double* d_odom) {
+  if (!h || T < 1 || m_max < 1 || m_max > kMaxAssoc || xy_stride < 2 || !d_counts || !d_xy ||
+      !d_odom)
+    return EKF_E_ARG;
+  if (!device_assoc_supported(h)) return EKF_E_ARG;
+  return replay_device_assoc(h, T, m_max, d_counts, d_xy, xy_stride, d_odom, nullptr, nullptr,
+                             nullptr);
+}
+
+int ekf_get_decisions(ekf_t h, int f, int m, int* assoc_out, int* is_new_out) {
+  if (!valid(h, f) || m < 0 || m > kMaxAssoc) return EKF_E_ARG;
+  if (int rc = settle(h)) return rc;
+  FilterCtl c;
+  HIPCHK(hipMemcpy(&c, h->ctl + f, sizeof(FilterCtl), hipMemcpyDeviceToHost));
+  for (int i = 0; i < m; ++i) {
+    if (assoc_out) assoc_out[i] = c.assoc_j[i];
+    if (is_new_out) is_new_out[i] = c.assoc_new[i];
+  }
+  return EKF_OK;
 }
 
 int ekf_predict(ekf_t h, int f) {

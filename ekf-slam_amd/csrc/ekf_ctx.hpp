@@ -91,6 +91,12 @@ struct ekf_ctx {
   hipStream_t plan_stream = nullptr;  // the stream the last device planner ran on
   unsigned plan_total = 0;    // kSyncPlan: descriptors device planners have counted so far
   unsigned need_plan = 0;     // the next chain launch polls kSyncPlan for this (0: none)
+  // lm_replay_into: the messages' odometry, staged in pinned memory (ev_odom: its last upload is
+  // done, the staging may be rewritten) and uploaded on the planning stream
+  double* odom_d = nullptr;
+  double* odom_h = nullptr;
+  size_t odom_cap = 0;  // doubles either holds
+  hipEvent_t ev_odom = nullptr;
   // the host mirror and the launch plan (ekf_set_joseph's form lives there too)
   ekfslam::Planner plan;
   std::vector<unsigned> held;    // status bits taken off the device word by the synchronous forms
@@ -147,5 +153,16 @@ int assoc_sync(ekf_ctx* h, int f0, int nf, bool predict, bool posterior, int m_m
                int* new_out);
 int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* d_ids,
                   const int* d_actions, const double* d_rel_xy, const double* d_odom);
+// the chunk routes only: pipeline handle, assoc_route(h) != EKF_ASSOC_MARKER
+inline bool device_assoc_supported(const ekf_ctx* h) {
+  return !h->resident && assoc_route(h) != EKF_ASSOC_MARKER;
+}
+// Unknown-association replay planned on the GPU (k_plan_assoc). host_odom (nullable): [T][F][3] on
+// the host, uploaded into the handle's own buffer and used instead of d_odom. ready (nullable):
+// the planning stream waits for it before the planner reads its inputs; planned (nullable):
+// recorded behind the planner kernel, after which the descriptors hold copies of every input.
+int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const double* d_xy,
+                        int xy_stride, const double* d_odom, const double* host_odom,
+                        hipEvent_t ready, hipEvent_t planned);
 
 }  // namespace ekfslam

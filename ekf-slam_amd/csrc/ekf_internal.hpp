@@ -1,5 +1,6 @@
-// Runtime internals shared by the filter runtime (ekf_sched.cpp) and the on-device simulator
-// (sim_api.cpp): how a device-written plan of known-association messages runs on a handle.
+// Runtime internals shared by the filter runtime (ekf_sched.cpp), the on-device simulator
+// (sim_api.cpp): how a device-written plan of known-association messages runs on a handle; and the
+// landmark front-end (lm_api.cpp): how its marker buffer becomes a device-planned association replay.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,5 +29,14 @@ int handle_parity(ekf_t h, int* parity);
 // predict input of the next host-planned call), no pending predict, and a non-pipelined next chunk.
 int run_device_plan(ekf_t h, const MsgDesc* dd, const PlanEntry* dplan, int T,
                     const int* parity_after, const double* odom_after);
+// The filter side of lm_replay_into (lm_api.cpp): ekf_replay_device_assoc on the front-end's
+// lm_marker[T·F][m_max] array (xy_stride 4) and counts on `device`, with the messages' odometry
+// odom[T][F][3] taken from the host into a buffer the handle owns. The planning stream waits for
+// `ready` (the front-end's detect) before the planner reads the markers; `planned` is recorded
+// behind the planner, after which the marker buffer is free again. EKF_E_ARG as the entry point's,
+// and for a handle on another device.
+int replay_markers(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                   const double* d_markers, const double* odom, hipEvent_t ready,
+                   hipEvent_t planned);
 
 }  // namespace ekfslam

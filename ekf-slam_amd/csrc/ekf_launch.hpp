@@ -146,6 +146,21 @@ struct ReplayArgs {
 };
 hipError_t launch_plan_replay(const ReplayArgs& a, hipStream_t s);
 
+// Unknown-association replay planned on the GPU (k_plan_assoc, ekf_replay_device_assoc): C =
+// ⌈M / kMaxChunk⌉ chunk descriptors per message, desc[(t·C + c)·F + f].
+struct AssocReplayArgs {
+  const int* counts;      // [T][F]; ≤ 0: no message, > M: clamped to M
+  const double* xy;       // marker i of (t, f): xy[((t·F + f)·M + i)·stride + {0, 1}]
+  const double* odom;     // [T][F][3]
+  const PlanState* st_in; // [F]
+  PlanState* st_out;      // [F]
+  MsgDesc* desc;          // [T][C][F]
+  int T, F, M, C;
+  int stride;             // doubles between markers (2: packed pairs, 4: lm_marker)
+  int joseph;             // 1: Joseph form (every chunk flagged kJoseph)
+};
+hipError_t launch_plan_assoc(const AssocReplayArgs& a, hipStream_t s);
+
 // Σ₀ diagonal: Σ[i][i] = v for i ≥ 3 (the rest is zero-filled by the caller).
 template <typename T>
 hipError_t launch_init_diag(T* sig, size_t stride, int n, int ld, double v, int nf, hipStream_t s);

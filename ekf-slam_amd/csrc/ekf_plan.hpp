@@ -1,8 +1,9 @@
 // The host planner: turns messages into MsgDesc descriptors and a launch list, and keeps the
 // per-filter mirror of what the device will hold once the plan has run (Σ parity, pending predict,
 // the last pipelined chunk, odometry). It sets every descriptor flag of the project; k_plan_replay
-// (plan_kernels.hip) reproduces known() byte for byte. Nothing here calls HIP, so it is tested on
-// the CPU alone (tests/test_plan_host.py).
+// (plan_kernels.hip) reproduces known() byte for byte, k_plan_assoc unknown() on a chunk route
+// (tests/test_plan_assoc_host.py). Nothing here calls HIP, so it is tested on the CPU alone
+// (tests/test_plan_host.py).
 #pragma once
 #include <array>
 #include <cstddef>

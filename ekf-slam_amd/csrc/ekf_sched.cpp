@@ -690,6 +690,97 @@ int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* 
   return issue_device_chunks(h, h->ddesc, T, false, h->stage != nullptr);
 }
 
+// Unknown-association replay whose inputs are already in device memory: k_plan_assoc writes the
+// C = ⌈m_max / kMaxChunk⌉ chunk descriptors of every message into the upload buffer, then chunk by
+// chunk the launches a host plan of kLaunchAssocChunk runs. The planner sits on the stream those
+// launches run on, ahead of them in stream order, so nothing has to count its descriptors; which
+// chunks are active only the device knows, and an inactive one costs its (empty) launch pair.
+int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const double* d_xy,
+                        int xy_stride, const double* d_odom, const double* host_odom,
+                        hipEvent_t ready, hipEvent_t planned) {
+  hipSetDevice(h->cfg.device);
+  if (int rc = flush(h)) return rc;  // what the host planned before runs first
+  const size_t F = static_cast<size_t>(h->F);
+  const int C = (m_max + kMaxChunk - 1) / kMaxChunk;
+  if (!h->dstate[0]) {
+    for (PlanState*& p : h->dstate)
+      if (hipMalloc(&p, F * sizeof(PlanState)) != hipSuccess) return EKF_E_NOMEM;
+    if (hipHostMalloc(reinterpret_cast<void**>(&h->hstate), F * sizeof(PlanState),
+                      hipHostMallocDefault) != hipSuccess)
+      return EKF_E_NOMEM;
+  }
+  if (int rc = reserve_device(h, static_cast<size_t>(T) * C * F)) return rc;
+  const size_t no = 3 * static_cast<size_t>(T) * F;
+  if (host_odom) {
+    if (!h->ev_odom) HIPCHK(hipEventCreateWithFlags(&h->ev_odom, hipEventDisableTiming));
+    if (no > h->odom_cap) {
+      if (drain(h)) return EKF_E_HIP;  // a planner in flight may still read the old buffer
+      if (h->odom_d) HIPCHK(hipFree(h->odom_d));
+      if (h->odom_h) HIPCHK(hipHostFree(h->odom_h));
+      h->odom_d = h->odom_h = nullptr;
+      h->odom_cap = 0;
+      const size_t cap = std::max(no, static_cast<size_t>(3 * 64) * F);
+      if (hipMalloc(&h->odom_d, cap * sizeof(double)) != hipSuccess ||
+          hipHostMalloc(reinterpret_cast<void**>(&h->odom_h), cap * sizeof(double),
+                        hipHostMallocDefault) != hipSuccess)
+        return EKF_E_NOMEM;
+      h->odom_cap = cap;
+    } else {
+      HIPCHK(hipEventSynchronize(h->ev_odom));  // the last upload has left the staging
+    }
+    std::memcpy(h->odom_h, host_odom, no * sizeof(double));
+  }
+  // The planner rewrites the upload buffer on the stream the association launches run on. Work on
+  // that stream is ahead of it in stream order; work on the main stream that the bulk stream is
+  // not ordered after yet (a chain, a k_posterior reading its descriptor) must end first: the hop a
+  // host-planned association chunk takes (assoc_msg_group), taken before the planner instead.
+  hipStream_t ps = h->serial ? h->stream : h->bulk;
+  if (!h->serial && (h->main_dirty || h->main_unordered) && fork_bulk_clean(h)) return EKF_E_HIP;
+  if (ready) HIPCHK(hipStreamWaitEvent(ps, ready, 0));
+  if (host_odom) {
+    HIPCHK(hipMemcpyAsync(h->odom_d, h->odom_h, no * sizeof(double), hipMemcpyHostToDevice, ps));
+    HIPCHK(hipEventRecord(h->ev_odom, ps));
+  }
+  if (!h->dev_plan) {  // the host mirror goes down once; later device replays chain on the device
+    h->plan.export_state(h->hstate);
+    HIPCHK(hipMemcpyAsync(h->dstate[h->dstate_cur], h->hstate, F * sizeof(PlanState),
+                          hipMemcpyHostToDevice, ps));
+    h->dev_plan = true;
+  }
+  AssocReplayArgs a{};
+  a.counts = d_counts;
+  a.xy = d_xy;
+  a.odom = host_odom ? h->odom_d : d_odom;
+  a.st_in = h->dstate[h->dstate_cur];
+  a.st_out = h->dstate[h->dstate_cur ^ 1];
+  a.desc = h->ddesc;
+  a.T = T;
+  a.F = h->F;
+  a.M = m_max;
+  a.C = C;
+  a.stride = xy_stride;
+  a.joseph = h->plan.joseph() ? 1 : 0;
+  HIPCHK(launch_plan_assoc(a, ps));
+  if (planned) HIPCHK(hipEventRecord(planned, ps));
+  h->dstate_cur ^= 1;
+  h->plan_stream = ps;
+  // a run of association chunks publishes its Σ epoch once, behind its last pass; as the last
+  // launch of a host plan, this run's last publishes none (the next flush joins the bulk stream)
+  int rc = EKF_OK;
+  for (size_t i = 0; i < static_cast<size_t>(T) * C && !rc; ++i)
+    rc = assoc_msg_group(h, h->ddesc + i * F, 0, h->F, false);
+  return rc;
+}
+
+int replay_markers(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                   const double* d_markers, const double* odom, hipEvent_t ready,
+                   hipEvent_t planned) {
+  if (!h || device != h->cfg.device || T < 1 || m_max < 1 || m_max > kMaxAssoc || !d_counts ||
+      !d_markers || !odom || !device_assoc_supported(h))
+    return EKF_E_ARG;
+  return replay_device_assoc(h, T, m_max, d_counts, d_markers, 4, nullptr, odom, ready, planned);
+}
+
 int handle_info(ekf_t h, HandleInfo* out) {
   if (!h || !out) return EKF_E_ARG;
   if (int rc = flush(h)) return rc;

@@ -1,11 +1,14 @@
 // Host runtime behind include/landmarks.h: device buffers, the handle's stream and the batched
 // laserCallback (nuslam/src/landmarks.cpp:109-156) over lm_kernels.hip, and the simulated laser
 // (nusim/src/nusim.cpp:559-710) over lidar_kernels.hip whose scans it can detect on in place.
+// lm_detect_device leaves the markers on the device, and lm_replay_into hands them to a filter
+// handle's device planner (k_plan_assoc) without a host hop.
 #include <hip/hip_runtime.h>
 
 #include <new>
 
 #include "ekf.h"
+#include "ekf_internal.hpp"
 #include "landmarks.h"
 #include "lm_launch.hpp"
 
@@ -35,6 +38,12 @@ struct lm_ctx {
   hipEvent_t e_up = nullptr, s0 = nullptr, s1 = nullptr;
   bool sim_timed = false;
   int res_scans = 0, res_beams = 0;  // 0: nothing resident
+  // lm_detect_device / lm_replay_into: the detect whose results stay in d_markers / d_counts
+  // (dev_scans scans of dev_cap markers; 0: none), the event behind it that a filter's planning
+  // stream waits for, and the event behind that planner which frees the marker buffer again
+  int dev_scans = 0, dev_cap = 0;
+  hipEvent_t e_det = nullptr, e_planned = nullptr;
+  bool planner_reads = false;  // e_planned is recorded and this stream has not waited for it yet
 };
 
 namespace {
@@ -70,10 +79,16 @@ int stage_clusters(lm_t h, int nc, const int* offs, const double* xy) {
   return EKF_OK;
 }
 
-// Landmarks::laserCallback over the S × B ranges (and angles) already in the handle's buffers.
-int run_detect(lm_t h, int S, int B, double thr, lm_marker* markers, int max_markers,
-               int* counts) {
+// Landmarks::laserCallback over the S × B ranges (and angles) already in the handle's buffers,
+// enqueued: markers [S][cap] and counts [S] stay on the device.
+int enqueue_detect(lm_t h, int S, int B, double thr, int max_markers) {
   const int cap = max_markers > 0 ? max_markers : 1;
+  h->dev_scans = 0;
+  if (h->planner_reads) {  // a filter's planner (lm_replay_into) may still read markers and counts
+    if (cap > h->marker_cap && hipEventSynchronize(h->e_planned) != hipSuccess) return EKF_E_HIP;
+    if (hipStreamWaitEvent(h->stream, h->e_planned, 0) != hipSuccess) return EKF_E_HIP;
+    h->planner_reads = false;
+  }
   if (cap > h->marker_cap) {
     if (grow(reinterpret_cast<void**>(&h->d_markers),
              sizeof(lm_marker) * static_cast<size_t>(h->max_scans) * cap))
@@ -86,6 +101,14 @@ int run_detect(lm_t h, int S, int B, double thr, lm_marker* markers, int max_mar
     return EKF_E_HIP;
   if (hipEventRecord(h->e1, h->stream) != hipSuccess) return EKF_E_HIP;
   h->timed = true;
+  return EKF_OK;
+}
+
+// ... and its results to the host (synchronising).
+int run_detect(lm_t h, int S, int B, double thr, lm_marker* markers, int max_markers,
+               int* counts) {
+  if (int rc = enqueue_detect(h, S, B, thr, max_markers)) return rc;
+  const int cap = max_markers > 0 ? max_markers : 1;
   if (hipMemcpyAsync(counts, h->d_counts, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream) !=
       hipSuccess)
     return EKF_E_HIP;
@@ -94,6 +117,21 @@ int run_detect(lm_t h, int S, int B, double thr, lm_marker* markers, int max_mar
                      hipMemcpyDeviceToHost, h->stream) != hipSuccess)
     return EKF_E_HIP;
   return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+}
+
+// A host caller's scans into the handle's buffers (enqueued).
+int upload_scans(lm_t h, int S, int B, const float* ranges, const double* amin,
+                 const double* ainc) {
+  h->res_scans = h->res_beams = 0;  // the upload overwrites lm_simulate's scans
+  const size_t nr = static_cast<size_t>(S) * B;
+  if (hipMemcpyAsync(h->d_ranges, ranges, sizeof(float) * nr, hipMemcpyHostToDevice, h->stream) !=
+          hipSuccess ||
+      hipMemcpyAsync(h->d_amin, amin, sizeof(double) * S, hipMemcpyHostToDevice, h->stream) !=
+          hipSuccess ||
+      hipMemcpyAsync(h->d_ainc, ainc, sizeof(double) * S, hipMemcpyHostToDevice, h->stream) !=
+          hipSuccess)
+    return EKF_E_HIP;
+  return EKF_OK;
 }
 
 }  // namespace
@@ -112,7 +150,9 @@ int lm_create(lm_t* out, int max_scans, int max_beams, int device) {
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess ||
       hipEventCreate(&h->e0) != hipSuccess || hipEventCreate(&h->e1) != hipSuccess ||
       hipEventCreate(&h->e_up) != hipSuccess || hipEventCreate(&h->s0) != hipSuccess ||
-      hipEventCreate(&h->s1) != hipSuccess) {
+      hipEventCreate(&h->s1) != hipSuccess ||
+      hipEventCreateWithFlags(&h->e_det, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&h->e_planned, hipEventDisableTiming) != hipSuccess) {
     lm_destroy(h);
     return EKF_E_HIP;
   }
@@ -140,6 +180,7 @@ int lm_destroy(lm_t h) {
   if (!h) return EKF_E_ARG;
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
+  if (h->planner_reads) hipEventSynchronize(h->e_planned);  // a filter's planner reads d_markers
   for (void* p : {static_cast<void*>(h->d_ranges), static_cast<void*>(h->d_amin),
                   static_cast<void*>(h->d_ainc), static_cast<void*>(h->d_counts),
                   static_cast<void*>(h->d_markers), static_cast<void*>(h->d_offs),
@@ -150,7 +191,7 @@ int lm_destroy(lm_t h) {
                   static_cast<void*>(h->d_poses), static_cast<void*>(h->d_scene),
                   static_cast<void*>(h->d_circles)})
     if (p) hipFree(p);
-  for (hipEvent_t e : {h->e0, h->e1, h->e_up, h->s0, h->s1})
+  for (hipEvent_t e : {h->e0, h->e1, h->e_up, h->s0, h->s1, h->e_det, h->e_planned})
     if (e) hipEventDestroy(e);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -163,15 +204,7 @@ int lm_detect(lm_t h, int S, int B, const float* ranges, const double* amin, con
       !ainc || !counts || max_markers < 0 || (max_markers > 0 && !markers))
     return EKF_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
-  h->res_scans = h->res_beams = 0;  // the upload overwrites lm_simulate's scans
-  const size_t nr = static_cast<size_t>(S) * B;
-  if (hipMemcpyAsync(h->d_ranges, ranges, sizeof(float) * nr, hipMemcpyHostToDevice, h->stream) !=
-          hipSuccess ||
-      hipMemcpyAsync(h->d_amin, amin, sizeof(double) * S, hipMemcpyHostToDevice, h->stream) !=
-          hipSuccess ||
-      hipMemcpyAsync(h->d_ainc, ainc, sizeof(double) * S, hipMemcpyHostToDevice, h->stream) !=
-          hipSuccess)
-    return EKF_E_HIP;
+  if (int rc = upload_scans(h, S, B, ranges, amin, ainc)) return rc;
   return run_detect(h, S, B, thr, markers, max_markers, counts);
 }
 
@@ -250,6 +283,64 @@ int lm_detect_resident(lm_t h, double thr, lm_marker* markers, int max_markers, 
     return EKF_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
   return run_detect(h, h->res_scans, h->res_beams, thr, markers, max_markers, counts);
+}
+
+int lm_detect_device(lm_t h, int S, int B, const float* ranges, const double* amin,
+                     const double* ainc, double thr, int max_markers) {
+  if (!h || max_markers < 1) return EKF_E_ARG;
+  if (ranges) {
+    if (S <= 0 || S > h->max_scans || B < 2 || B > h->max_beams || !amin || !ainc) return EKF_E_ARG;
+  } else if (h->res_scans <= 0) {
+    return EKF_E_ARG;
+  }
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  if (ranges) {
+    if (int rc = upload_scans(h, S, B, ranges, amin, ainc)) return rc;
+    if (hipEventRecord(h->e_up, h->stream) != hipSuccess) return EKF_E_HIP;
+  } else {
+    S = h->res_scans;
+    B = h->res_beams;
+  }
+  if (int rc = enqueue_detect(h, S, B, thr, max_markers)) return rc;
+  if (hipEventRecord(h->e_det, h->stream) != hipSuccess) return EKF_E_HIP;
+  // the caller's scans are consumed (they may be freed); the detect itself is still in flight
+  if (ranges && hipEventSynchronize(h->e_up) != hipSuccess) return EKF_E_HIP;
+  h->dev_scans = S;
+  h->dev_cap = max_markers;
+  return EKF_OK;
+}
+
+int lm_fetch_markers(lm_t h, lm_marker* markers, int max_markers, int* counts) {
+  if (!h || h->dev_scans <= 0 || max_markers < 0 || (max_markers > 0 && !markers) ||
+      (max_markers == 0 && !counts))
+    return EKF_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  const int S = h->dev_scans, w = max_markers < h->dev_cap ? max_markers : h->dev_cap;
+  if (counts && hipMemcpyAsync(counts, h->d_counts, sizeof(int) * S, hipMemcpyDeviceToHost,
+                               h->stream) != hipSuccess)
+    return EKF_E_HIP;
+  if (w > 0 && hipMemcpy2DAsync(markers, sizeof(lm_marker) * max_markers, h->d_markers,
+                                sizeof(lm_marker) * h->dev_cap, sizeof(lm_marker) * w, S,
+                                hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+    return EKF_E_HIP;
+  return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+}
+
+static_assert(sizeof(lm_marker) == 4 * sizeof(double), "k_plan_assoc reads lm_marker at stride 4");
+
+int lm_replay_into(lm_t h, ekf_t e, int T, const double* odom) {
+  if (!h || !e || T < 1 || !odom || h->dev_scans <= 0) return EKF_E_ARG;
+  int F = 0;
+  if (ekf_dims(e, nullptr, nullptr, &F) != EKF_OK || F < 1 ||
+      static_cast<long long>(T) * F != h->dev_scans || h->dev_cap > 64)
+    return EKF_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  const int rc = ekfslam::replay_markers(e, h->device, T, h->dev_cap, h->d_counts,
+                                         reinterpret_cast<const double*>(h->d_markers), odom,
+                                         h->e_det, h->e_planned);
+  // (an argument error comes back before anything is enqueued; past that the planner may be)
+  if (rc != EKF_E_ARG) h->planner_reads = true;
+  return rc;
 }
 
 int lm_last_simulate_us(lm_t h, double* us) {

@@ -9,11 +9,14 @@
 // A message with count 0 is no message (ekf_batch_sensor: the filter sits the step out); one
 // whose markers are all DELETE is a predict + posterior (slam.cpp:205), as on the host.
 // Joseph form (A.joseph = 1): the same chunks, flagged kJoseph (kMaxJoseph = kMaxChunk markers).
+//
+// Unknown-association replays (ekf_replay_device_assoc): k_plan_assoc at the end of this file.
 #include <hip/hip_runtime.h>
 
 #include "ekf.h"
 #include "ekf_device.hpp"
 #include "ekf_launch.hpp"
+#include "plan_assoc.hpp"
 
 namespace ekfslam {
 namespace {
@@ -170,6 +173,86 @@ __global__ __launch_bounds__(64) void k_plan_replay(ReplayArgs A) {
 hipError_t launch_plan_replay(const ReplayArgs& a, hipStream_t s) {
   if (a.T <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_plan_replay, dim3(a.T, a.F), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+// Unknown-association replay planned on the GPU (ekf_replay_device_assoc): one wave per (message
+// t, chunk c, filter f) writes desc[(t·C + c)·F + f], the MsgDesc Planner::unknown writes on the
+// host for the same message on a chunk route (kLaunchAssocChunk, predict = posterior = true).
+// Association chunks run unpipelined, so a descriptor depends on the chunks before it through the
+// Σ parity alone: a wave scan over the earlier counts finds it. A message with count ≤ 0 is no
+// message (every chunk descriptor of it all zero: k_assoc_msg and the Σ pass return at once); a
+// count above M is clamped to M (the markers beyond were counted, not written). The scalar fields
+// come from plan_assoc (plan_assoc.hpp), which the CPU test holds against the host planner.
+// No count is published: the planner runs on the stream that runs the association launches.
+__global__ __launch_bounds__(64) void k_plan_assoc(AssocReplayArgs A) {
+  __shared__ MsgDesc sd;
+  const int t = blockIdx.x, c = blockIdx.y, f = blockIdx.z, lane = threadIdx.x;
+  const int F = A.F, M = A.M, T = A.T;
+  const size_t tf = static_cast<size_t>(t) * F + f;
+  auto cnt = [&](int tt) { return A.counts[static_cast<size_t>(tt) * F + f]; };
+  // active chunks of the filter in the messages before t: at most 4 a message (M ≤ kMaxAssoc), so
+  // three ballots a round count them, 64 messages a round
+  int earlier = 0;
+  for (int base = 0; base < t; base += 64) {
+    const int tt = base + lane;
+    const int n = tt < t ? min(cnt(tt), M) : 0;
+    const int nc = n > 0 ? (n + kMaxChunk - 1) / kMaxChunk : 0;
+    earlier += __popcll(__ballot(nc & 1)) + 2 * __popcll(__ballot(nc & 2)) +
+               4 * __popcll(__ballot(nc & 4));
+  }
+  const PlanState& s0 = A.st_in[f];
+  const int my = cnt(t);
+  const int mi = kMaxChunk * c + lane;  // the lane's marker of the message
+  const bool has = lane < kMaxChunk && mi < min(my, M);
+  double x = 0.0, y = 0.0;
+  if (has) {
+    const size_t o = (tf * M + mi) * static_cast<size_t>(A.stride);
+    x = A.xy[o];
+    y = A.xy[o + 1];
+  }
+  const double od = lane < 3 ? A.odom[tf * 3 + lane] : 0.0;
+  const AssocPlan p = plan_assoc(my, M, c, has ? lane : -1, x, y, earlier, A.joseph != 0,
+                                 s0.parity, s0.prev_m, s0.pending);
+  uint4* dz = reinterpret_cast<uint4*>(&sd);
+  for (int e = lane; e < static_cast<int>(sizeof(MsgDesc) / 16); e += 64) dz[e] = uint4{0, 0, 0, 0};
+  __syncthreads();
+  if (p.active) {
+    if (lane < kMaxChunk) {
+      sd.ids[lane] = p.id;
+      sd.z[lane][0] = p.zr;
+      sd.z[lane][1] = p.zb;
+    }
+    if (lane < 3) sd.odom[lane] = od;
+    if (lane == 0) {
+      sd.m = p.m;
+      sd.flags = p.flags;
+      sd.parity = p.parity;
+      sd.assoc_slot = p.assoc_slot;
+    }
+  }
+  __syncthreads();
+  uint4* gd = reinterpret_cast<uint4*>(A.desc + (static_cast<size_t>(t) * A.C + c) * F + f);
+  for (int e = lane; e < static_cast<int>(sizeof(MsgDesc) / 16); e += 64) gd[e] = dz[e];
+  // ---- the filter's state after the replay (the host adopts it lazily) ----
+  if (t == T - 1 && c == 0) {
+    PlanState& so = A.st_out[f];
+    if (lane == 0) {
+      so.parity = p.st_parity;
+      so.prev_m = p.st_prev_m;
+      so.pending = p.st_pending;
+      so.pad = 0;
+      so.pad2 = 0.0;
+    }
+    if (lane < kMaxChunk) so.prev_ids[lane] = s0.prev_ids[lane];
+    if (lane < 3) so.odom[lane] = od;  // t_odom_robot of the last message, active or not
+  }
+}
+
+hipError_t launch_plan_assoc(const AssocReplayArgs& a, hipStream_t s) {
+  if (a.T <= 0 || a.C <= 0 || a.F <= 0) return hipSuccess;
+  if (a.F > 65535) return hipErrorInvalidValue;  // (grid z)
+  hipLaunchKernelGGL(k_plan_assoc, dim3(a.T, a.C, a.F), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

@@ -32,6 +32,7 @@ EXPORTS = [
     "ekf_get_assoc_route", "ekf_get_schedule",
     "ekf_set_odom",
     "ekf_fake_sensor", "ekf_sensor", "ekf_batch_sensor", "ekf_replay", "ekf_replay_device",
+    "ekf_replay_device_assoc", "ekf_get_decisions",
     "ekf_predict",
     "ekf_correct", "ekf_associate_correct", "ekf_posterior", "ekf_sync", "ekf_flush", "ekf_get_pose",
     "ekf_get_map_odom", "ekf_get_state", "ekf_set_state", "ekf_get_status", "ekf_defer",
@@ -44,6 +45,7 @@ EXPORTS = [
     "lm_create", "lm_destroy", "lm_detect", "lm_fit_circles", "lm_check_circles",
     "lm_last_kernel_us",
     "lm_scan_config_default", "lm_simulate", "lm_detect_resident", "lm_last_simulate_us",
+    "lm_detect_device", "lm_fetch_markers", "lm_replay_into",
     "ekf_sim_config_default", "ekf_sim_create", "ekf_sim_destroy", "ekf_sim_run",
     "ekf_sim_markers", "ekf_sim_poses",
 ]
@@ -104,6 +106,8 @@ def lib():
             "ekf_batch_sensor": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
             "ekf_replay": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
             "ekf_replay_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+            "ekf_replay_device_assoc": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp]),
+            "ekf_get_decisions": (_i, [_vp, _i, _i, _vp, _vp]),
             "ekf_predict": (_i, [_vp, _i]),
             "ekf_correct": (_i, [_vp, _i, _i, _d, _d]),
             "ekf_associate_correct": (_i, [_vp, _i, _d, _d, _ip, _ip]),
@@ -144,6 +148,9 @@ def lib():
             "lm_simulate": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, C.POINTER(ScanConfig), _vp]),
             "lm_detect_resident": (_i, [_vp, _d, _vp, _i, _vp]),
             "lm_last_simulate_us": (_i, [_vp, _dp]),
+            "lm_detect_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d, _i]),
+            "lm_fetch_markers": (_i, [_vp, _vp, _i, _vp]),
+            "lm_replay_into": (_i, [_vp, _vp, _i, _vp]),
             "ekf_sim_config_default": (None, [C.POINTER(SimConfig)]),
             "ekf_sim_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(SimConfig), _i, _vp]),
             "ekf_sim_destroy": (_i, [_vp]),
@@ -278,6 +285,35 @@ class EKF:
         no tensor work on the caller's path (bench.py's timed region)."""
         _check(lib().ekf_replay_device(self.h, T, M, counts, ids, actions or None, rel_xy, odom),
                "ekf_replay_device")
+
+    def replay_device_assoc(self, counts, xy, odom, stride=None):
+        """ekf_replay_device_assoc: unknown-association replay whose inputs are GPU tensors already
+        on this handle's device — counts [T,F] int32 (<= 0: no message), xy [T,F,M,2] float64
+        (packed pairs) or [T,F,M,4] (lm_marker rows: x, y first), odom [T,F,3] float64; M <= 64.
+        ``stride``: doubles between markers, by default xy.shape[-1]. Asynchronous; keep the
+        tensors alive until a sync."""
+        import torch
+        T, M = int(xy.shape[0]), int(xy.shape[2])
+        stride = int(xy.shape[-1]) if stride is None else int(stride)
+        if stride not in (2, 4):
+            raise ValueError("xy must hold 2 (packed) or 4 (lm_marker) doubles per marker")
+        _check(lib().ekf_replay_device_assoc(self.h, T, M, _dptr(counts, torch.int32),
+                                             _dptr(xy, torch.float64), stride,
+                                             _dptr(odom, torch.float64)),
+               "ekf_replay_device_assoc")
+
+    def replay_device_assoc_raw(self, T, M, counts, xy, stride, odom):
+        """ekf_replay_device_assoc on raw device addresses (ints); returns the status code."""
+        return lib().ekf_replay_device_assoc(self.h, T, M, counts or None, xy or None, stride,
+                                             odom or None)
+
+    def decisions(self, m, f=0):
+        """ekf_get_decisions: (assoc [m], is_new [m]) of filter f's most recent unknown-association
+        message (m <= 64). Synchronises."""
+        j = np.zeros(max(m, 1), np.int32)
+        nw = np.zeros(max(m, 1), np.int32)
+        _check(lib().ekf_get_decisions(self.h, f, m, _ptr(j), _ptr(nw)), "ekf_get_decisions")
+        return j[:m], nw[:m]
 
     # fine-grained
     def predict(self, f=0):

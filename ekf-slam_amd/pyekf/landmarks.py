@@ -122,6 +122,47 @@ class Detector:
                                         cnt.ctypes.data), "lm_detect_resident")
         return cnt, out
 
+    def detect_device(self, ranges=None, angle_min=0.0, angle_inc=0.0, threshold=0.2,
+                      max_markers=32):
+        """lm_detect_device: ``detect`` whose markers and counts stay on the device (asynchronous).
+        ``ranges`` None: on the scans the last ``simulate`` left there. Returns the scan count."""
+        if ranges is None:
+            S = self._resident
+            _check(lib().lm_detect_device(self.h, 0, 0, None, None, None, threshold, max_markers),
+                   "lm_detect_device")
+        else:
+            r = np.ascontiguousarray(ranges, dtype=np.float32)
+            if r.ndim == 1:
+                r = r[None]
+            S, B = r.shape
+            am = np.ascontiguousarray(np.broadcast_to(np.asarray(angle_min, np.float64), (S,)))
+            ai = np.ascontiguousarray(np.broadcast_to(np.asarray(angle_inc, np.float64), (S,)))
+            _check(lib().lm_detect_device(self.h, S, B, r.ctypes.data, am.ctypes.data,
+                                          ai.ctypes.data, threshold, max_markers),
+                   "lm_detect_device")
+        self._device = (S, max_markers)
+        return S
+
+    def fetch_markers(self, max_markers=None):
+        """lm_fetch_markers: (counts [S], markers [S, max_markers]) of the last ``detect_device``
+        (synchronising)."""
+        S, cap = getattr(self, "_device", (1, 1))
+        mm = cap if max_markers is None else max_markers
+        out = np.zeros((S, mm), dtype=MARKER_DTYPE)
+        cnt = np.zeros(S, dtype=np.int32)
+        _check(lib().lm_fetch_markers(self.h, out.ctypes.data, mm, cnt.ctypes.data),
+               "lm_fetch_markers")
+        return cnt, out
+
+    def replay_into(self, ekf, T, odom):
+        """lm_replay_into: the last ``detect_device``'s scans as T unknown-association messages of
+        ``ekf``'s F filters (scan t·F + f is message t of filter f), odom [T, F, 3] on the host.
+        Asynchronous on both handles; returns the status code."""
+        od = np.ascontiguousarray(odom, dtype=np.float64)
+        if od.size != 3 * T * ekf.F:
+            raise ValueError("odom must be [T, F, 3]")
+        return lib().lm_replay_into(self.h, ekf.h, T, od.ctypes.data)
+
     def last_simulate_us(self):
         us = C.c_double()
         _check(lib().lm_last_simulate_us(self.h, C.byref(us)), "lm_last_simulate_us")

@@ -167,6 +167,40 @@ int ekf_replay(ekf_t h, int assoc, int T, int m_max, const int* counts, const in
 int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int* d_ids,
                       const int* d_actions, const double* d_rel_xy, const double* d_odom);
 
+/* ekf_replay with unknown association (assoc = 1, Slam::sensor_cb, slam.cpp:318-530, per message)
+ * whose inputs already live in device memory of the handle's GPU: the chunk descriptors are
+ * planned on the GPU and no input crosses PCIe.
+ *   d_counts  [T][F] int. A count <= 0 is no message: `landmarks` published nothing for that scan
+ *             (an empty detection, landmarks.cpp:153, or LM_NO_BREAK = -1) and nothing of the
+ *             filter changes. A count above m_max is clamped to m_max: lm_detect counts the
+ *             markers beyond its capacity but does not write them.
+ *   d_xy      marker i of message t of filter f is the two doubles at
+ *             d_xy[((t*F + f)*m_max + i)*xy_stride + {0, 1}]: xy_stride = 2 is rel_xy[T][F][m_max][2],
+ *             xy_stride = 4 an lm_marker[T*F][m_max] array read in place (landmarks.h).
+ *   d_odom    [T][F][3], t_odom_robot per message.
+ * 1 <= m_max <= 64, so that a message's decisions all stay readable (ekf_get_decisions).
+ * Pipeline handles on a chunk route only (ekf_get_assoc_route: EKF_ASSOC_CHUNK or
+ * EKF_ASSOC_CHUNK_XCD), either form, both dtypes. EKF_E_ARG, and nothing changes: a resident
+ * handle, the one-marker route, T < 1, m_max outside [1, 64], xy_stride < 2, a NULL d_counts /
+ * d_xy / d_odom. The measurement (range, bearing) of slam.cpp:346-347 is computed on the GPU:
+ * the range with a correctly rounded sqrt, the bearing's atan2 in double-double arithmetic and
+ * rounded once, so it can differ from glibc's only in the last bit and only where glibc's own is
+ * not the correctly rounded value (about one argument in a thousand).
+ * Every message costs ceil(m_max / 16) launch pairs whatever its count, so choose m_max no larger
+ * than needed. Asynchronous; the inputs must stay valid until the next synchronising call
+ * (ekf_sync, a state read). A full map and skipped markers are reported through ekf_get_status.
+ * The handle's planning state comes back to the host at the next host-planned call or state
+ * access. */
+int ekf_replay_device_assoc(ekf_t h, int T, int m_max, const int* d_counts, const double* d_xy,
+                            int xy_stride, const double* d_odom);
+
+/* The decisions (slam.cpp:344-440) of `filter`'s most recent unknown-association message, its
+ * first m <= 64 markers: assoc_out[i] = landmark slot, or -1 when the marker met a full map;
+ * is_new_out[i] = 1 when it opened that slot. Either output may be NULL. After ekf_sensor,
+ * ekf_batch_sensor / ekf_replay with assoc = 1, ekf_replay_device_assoc or lm_replay_into; markers
+ * beyond the message's own count hold an earlier message's decisions. Synchronises. */
+int ekf_get_decisions(ekf_t h, int filter, int m, int* assoc_out, int* is_new_out);
+
 /* ---- the finer-grained surface (north_star: predict()/update()/associate()) ---- */
 
 /* Predict (slam.cpp:184-198): deferred and folded into the next Σ pass. */

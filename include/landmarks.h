@@ -15,6 +15,7 @@
  */
 #ifndef EKFSLAM_LANDMARKS_H
 #define EKFSLAM_LANDMARKS_H
+#include "ekf.h" /* status codes, ekf_t (lm_replay_into) */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -96,6 +97,33 @@ int lm_simulate(lm_t h, int n_scans, int n_beams, const double* poses, int n_sce
 int lm_detect_resident(lm_t h, double threshold, lm_marker* markers, int max_markers, int* counts);
 /* Device time of the last lm_simulate's kernel (HIP events around the dispatch), microseconds. */
 int lm_last_simulate_us(lm_t h, double* us);
+
+/* ---- scans to posterior without a host hop ---- */
+
+/* lm_detect without the copy back: markers [n_scans][max_markers] and counts [n_scans] stay in
+ * the handle (1 <= max_markers). Asynchronous: the call returns once the caller's scans are
+ * uploaded (they may be freed), the detection still in flight on the handle's stream.
+ * ranges == NULL: detect on the resident scans of the last lm_simulate (as lm_detect_resident;
+ * n_scans, n_beams and the angle arrays are then ignored). The results stay until the handle's
+ * next detect of any form. */
+int lm_detect_device(lm_t h, int n_scans, int n_beams, const float* ranges,
+                     const double* angle_min, const double* angle_inc, double threshold,
+                     int max_markers);
+/* The last lm_detect_device's results to the host (synchronising; for tests and inspection):
+ * counts [n_scans] (nullable when markers are asked for), markers [n_scans][max_markers]
+ * (columns beyond the detect's own max_markers are left untouched). */
+int lm_fetch_markers(lm_t h, lm_marker* markers, int max_markers, int* counts);
+/* Feed them to a filter handle on the same device as T messages of unknown association
+ * (ekf_replay_device_assoc, ekf.h: Slam::sensor_cb per message): scan s = t*F + f is message t of
+ * filter f, so n_scans of the last lm_detect_device must equal T*F, and m_max = its max_markers
+ * (<= 64). odom[T][F][3] on the host, t_odom_robot per message (copied before the call returns).
+ * A scan that published nothing (count 0 or LM_NO_BREAK, landmarks.cpp:153) is no message; a
+ * count above max_markers is clamped to it. The filter's planning stream waits on the device for
+ * the detection, and the handle's next detect waits on the device until the filter has planned
+ * from the marker buffer: asynchronous on both handles, nothing crosses PCIe but odom.
+ * EKF_E_ARG: nothing detected yet, T*F != n_scans, max_markers > 64, handles on different
+ * devices, or a filter handle ekf_replay_device_assoc refuses. */
+int lm_replay_into(lm_t h, ekf_t e, int T, const double* odom);
 
 #ifdef __cplusplus
 }
