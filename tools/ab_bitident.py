@@ -3,8 +3,9 @@
   python tools/ab_bitident.py <libA.so> <libB.so>   (names inside ekf-slam_amd/, EKF_LIB)
 
 Each library runs the same replays in its own child process (the headline fp32 N = 1024 device
-replay from an fp64 survey, fp64 N = 1024, messages of two chunks, the Joseph form, four filters
-with event hand-offs, unknown association); the final states are compared bit for bit. A pure
+replay from an fp64 survey, fp64 N = 1024, messages of two chunks, the Joseph form, the rebuild
+without staged operands, the Joseph form in fp32 and under unknown association, four filters with
+event hand-offs, unknown association); the final states are compared bit for bit. A pure
 performance change of the kernels (same formulas, same summation order) must print "identical"."""
 import os
 import subprocess
@@ -75,6 +76,31 @@ def child(tag):
              actions=sc.actions[:, None])
     keep("joseph", e)
     e.close()
+    # k_chain branches the legs above leave out, on the same messages. The rebuild from operands
+    # the chain gathers itself (EKF_STAGE=0: no staged image, store_raw_image) ...
+    for name, dt in (("nostage64", pyekf.EKF_F64), ("nostage32", pyekf.EKF_F32)):
+        env(EKF_STAGE="0")
+        e = pyekf.EKF(n_landmarks=96, dtype=dt)
+        e.replay(sc.count[:, None], sc.rel[:, None], odom[:, None], ids=sc.ids[:, None],
+                 actions=sc.actions[:, None])
+        keep(name, e)
+        e.close()
+    # ... the Joseph form in fp32 (its pend patch carries the V·Kᵀ term) ...
+    env()
+    e = pyekf.EKF(n_landmarks=96, dtype=pyekf.EKF_F32)
+    e.set_joseph(True)
+    e.replay(sc.count[:, None], sc.rel[:, None], odom[:, None], ids=sc.ids[:, None],
+             actions=sc.actions[:, None])
+    keep("joseph32", e)
+    e.close()
+    # ... and unknown association with the Joseph form on (kNoInit chunks of the Joseph chain)
+    for name, dt in (("assoc_joseph64", pyekf.EKF_F64), ("assoc_joseph32", pyekf.EKF_F32)):
+        e = pyekf.EKF(n_landmarks=96, dtype=dt)
+        e.set_joseph(True)
+        e.replay(sc.count[:, None], sc.rel[:, None], odom[:, None], ids=None,
+                 actions=sc.actions[:, None], assoc=True)
+        keep(name, e)
+        e.close()
     # four filters, N = 256, events; and one stream
     sc = synth.synthetic(256, 20)
     odom = pyekf.odometry(sc)
