@@ -192,6 +192,13 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
   const int hi = __builtin_amdgcn_readlane(static_cast<int>(x >> 32), l);
   return __hiloint2double(hi, lo);
 }
+// the first active lane's double, wave-uniform (v_readfirstlane ×2)
+__device__ __forceinline__ double readfirstlane_f64(double v) {
+  const long long x = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readfirstlane(static_cast<int>(x));
+  const int hi = __builtin_amdgcn_readfirstlane(static_cast<int>(x >> 32));
+  return __hiloint2double(hi, lo);
+}
 
 // wave argmin of (d, k): the smaller d, ties (and two +inf) to the lower k. A strict total order
 // on the pairs, so any reduction tree gives the same pair: DPP row shifts 1, 2, 4, 8 (lane 15 of

@@ -5,7 +5,9 @@
 Each library runs the same replays in its own child process (the headline fp32 N = 1024 device
 replay from an fp64 survey, fp64 N = 1024, messages of two chunks, the Joseph form, the rebuild
 without staged operands, the Joseph form in fp32 and under unknown association, four filters with
-event hand-offs, unknown association); the final states are compared bit for bit. A pure
+event hand-offs, unknown association and its routes: one marker per launch, one workgroup, three
+on each transport, a map that fills, messages of two chunks); the final states are compared bit
+for bit. A pure
 performance change of the kernels (same formulas, same summation order) must print "identical"."""
 import os
 import subprocess
@@ -24,7 +26,8 @@ def child(tag):
     res = {}
 
     def env(**kv):
-        for k in ("EKF_SERIAL", "EKF_DEVSYNC", "EKF_STAGE", "EKF_CU_SPLIT"):
+        for k in ("EKF_SERIAL", "EKF_DEVSYNC", "EKF_STAGE", "EKF_CU_SPLIT", "EKF_RESIDENT",
+                  "EKF_AM_XCD", "EKF_ASSOC_MSG"):
             os.environ.pop(k, None)
         os.environ.update(kv)
 
@@ -121,6 +124,36 @@ def child(tag):
                  actions=sc.actions[:, None], assoc=True)
         keep(name, e)
         e.close()
+    # k_assoc_msg's and k_assoc's branches the legs above leave out, fp64 and fp32 each
+    def assoc_leg(name, N, sc, **kv):
+        env(**kv)
+        odom = pyekf.odometry(sc)
+        for sfx, dt in (("64", pyekf.EKF_F64), ("32", pyekf.EKF_F32)):
+            e = pyekf.EKF(n_landmarks=N, dtype=dt)
+            e.replay(sc.count[:, None], sc.rel[:, None], odom[:, None], ids=None,
+                     actions=sc.actions[:, None], assoc=True)
+            keep(name + sfx, e)
+            e.close()
+
+    # ... the one-marker route (k_assoc) on the messages above ...
+    assoc_leg("assoc_marker", 96, sc, EKF_ASSOC_MSG="0")
+    # ... one workgroup on the pipeline (G == 1: v_readlane instead of the tables) ...
+    sc20 = synth.make_scenario(20, synth.random_landmarks(12, seed=7), 10, max_markers=16, seed=14,
+                               shuffle=True)
+    assoc_leg("assoc_1wg", 20, sc20, EKF_RESIDENT="0", EKF_AM_XCD="0")
+    # ... three workgroups on each transport ...
+    sc130 = synth.make_scenario(130, synth.random_landmarks(100, seed=11), 10, max_markers=16,
+                                seed=18, shuffle=True)
+    assoc_leg("assoc_3wg_xcd", 130, sc130, EKF_AM_XCD="1")
+    assoc_leg("assoc_3wg_agent", 130, sc130, EKF_AM_XCD="0")
+    # ... a map that fills during the run (the drives sight 8 / 130 landmarks, the filters hold
+    # 3 / 70: later markers are skipped with EKF_FLAG_RANGE), one and two workgroups ...
+    assoc_leg("assoc_fill_1wg", 3, synth.make_scenario(8, synth.random_landmarks(8, seed=9), 12,
+                                                       max_markers=8, seed=10, shuffle=True),
+              EKF_RESIDENT="0")
+    assoc_leg("assoc_fill_2wg", 70, synth.populated(130, 6, shuffle=True), EKF_RESIDENT="0")
+    # ... and messages of two chunks (24 markers) under association
+    assoc_leg("assoc_multi", 96, synth.synthetic(96, 14, max_markers=24, shuffle=True))
     # digests only (a whole fp64 Σ at N = 1024 is 34 MB): bit-identical ⇔ equal digests
     import hashlib
     import json
