@@ -119,7 +119,7 @@ hipError_t launch_assoc_msg(const PassArgs<T>& a, const AmArgs& b, int n_filters
 template <typename T>
 hipError_t launch_posterior(const PassArgs<T>& a, int n_filters, hipStream_t s);
 
-// Resident path (ekf_resident.hip): n ≤ kResidentMaxN, fp64. One 1024-thread workgroup per filter
+// Resident path (ekf_resident.hip): n ≤ kResidentMaxN, fp64. One 256-thread workgroup per filter
 // [flo, flo + nfil) keeps Σ and x in registers across every entry of the plan (PlanEntry,
 // ekf_device.hpp).
 constexpr int kResidentMaxN = 128;

@@ -68,6 +68,16 @@ __device__ __forceinline__ double rsq_refined(double x) {
   return fma(y, e, y);
 }
 
+// The offset to a landmark, its squared range d and d^-½: what range_bearing and range_innovation
+// both start from.
+__device__ __forceinline__ void range_parts(const double* pose, double lx, double ly, double* ex,
+                                            double* ey, double* d, double* isd) {
+  *ex = lx - pose[1];
+  *ey = ly - pose[2];
+  *d = *ex * *ex + *ey * *ey;
+  *isd = rsq_refined(*d);
+}
+
 // Range-bearing model for landmark at (lx, ly) seen from pose: ẑ and the 2×5 H over
 // {θ, x, y, jx, jy} (slam.cpp:219-249).
 // bear_raw / bear_ok: the bearing before normalisation and whether the branch-free normalisation
@@ -75,9 +85,9 @@ __device__ __forceinline__ double rsq_refined(double x) {
 __device__ __forceinline__ void range_bearing(const double* pose, double lx, double ly,
                                               double* zhat, double* H0, double* H1,
                                               double* bear_raw, bool* bear_ok) {
-  const double ex = lx - pose[1], ey = ly - pose[2];
-  const double d = ex * ex + ey * ey;
-  const double isd = rsq_refined(d), id = isd * isd;
+  double ex, ey, d, isd;
+  range_parts(pose, lx, ly, &ex, &ey, &d, &isd);
+  const double id = isd * isd;
   zhat[0] = d * isd;
   *bear_raw = atan2_fast(ey, ex) - pose[0];
   zhat[1] = normalize_angle_near(*bear_raw, bear_ok);
@@ -91,6 +101,23 @@ __device__ __forceinline__ void range_bearing(const double* pose, double lx, dou
   H1[2] = -ex * id;
   H1[3] = -ey * id;
   H1[4] = ex * id;
+}
+
+// The range innovation z0 − ẑ0 with ẑ0 = d·d^-½ (range_bearing's zhat[0]) in one rounding, and the
+// same difference rounded after the product. A kernel that has evaluated z0 − zhat[0] one way
+// calls the matching one, so that the compiler's choice (it contracts the two or not, depending on
+// whether its SLP vectoriser pairs the range and bearing differences) cannot move with the code
+// around it. sub_rounded relies on `fp contract(off)` holding for the inlined subtraction;
+// checked through bit-identity of the resident kernel's results on this compiler only.
+__device__ __forceinline__ double range_innovation(const double* pose, double lx, double ly,
+                                                   double z0) {
+  double ex, ey, d, isd;
+  range_parts(pose, lx, ly, &ex, &ey, &d, &isd);
+  return fma(-d, isd, z0);
+}
+__device__ __forceinline__ double sub_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  return a - b;
 }
 
 // arma::inv on a 2×2 (closed form: adjugate / det, one reciprocal). false if singular / non-finite.

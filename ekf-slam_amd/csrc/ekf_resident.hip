@@ -13,13 +13,30 @@
 //            operands in every thread, so the same bits) and applies Σ ← Σ − K·(HΣ) and x += Kν
 //            to the elements it owns: 2 FMAs per element, no LDS traffic for Σ itself.
 // The Mahalanobis association of a marker (slam.cpp:344-440) is one wavefront: lane k scores
-// landmark k from the gathered pose rows / columns, the 2×2 landmark blocks and x, then a
-// 64-lane shuffle argmin (first index wins, like arma::index_min).
+// landmark k from the gathered pose rows / columns, the 2×2 landmark blocks and x, then a DPP
+// wave argmin (wave_argmin, ekf_math.hpp; first index wins, like arma::index_min).
 //
 // Numerics follow the chain kernel's helpers (range_bearing, inv2, rank2_sub, normalize_angle_near)
 // and k_assoc's distance expression, so decisions match the HBM pipeline's; Σ differs from it by
-// summation order only (Σ_ij − K_i0·M_0j − K_i1·M_1j as two FMAs; tests/test_gpu_resident.py: both
-// paths against the oracle).
+// summation order only (Σ_ij − K_i0·M_0j − K_i1·M_1j as two FMAs; tests/test_gpu_resident.py:
+// both paths against the oracle).
+//
+// In the source, in execution order. k_resident is the plan walk; a thread's share of the filter
+// is one ResState, and every phase is a __forceinline__ function on it (one register allocation):
+//   stage_plan_block      16 plan entries' descriptors → LDS
+//   load_filter           first entry naming the filter: Σ, x, t_map_odom, counter
+//   posterior_now / _from the deferred posterior t_map_odom (with the next gather of the pose)
+//   predict               gather_rows (pose) → barrier → Σ = AΣAᵀ + Q̄, the new pose
+//   known ids, per marker: gather_rows → barrier → correct
+//   unknown, per marker   associate_correct: gather_rows (pose), gather_assoc_blocks → barrier →
+//                         score_and_decide (wave 0) → barrier → init_new_landmark → gather_rows
+//                         (landmark) → barrier → correct
+//   correct               innovation_gain (ẑ, H, M = HΣ, S, S⁻¹, ν, K) → apply_simple /
+//                         apply_joseph → x += Kν
+//   store_filter          decisions, Σ, x, t_map_odom, counter, status
+// Shared algebra: times_H (five-term products with H), gain (K = q·S⁻¹), landmark_from (a first
+// sighting's position); range_innovation and sub_rounded (ekf_math.hpp) pin the two roundings of
+// z₀ − ẑ₀.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -60,7 +77,6 @@ typedef unsigned u2 __attribute__((ext_vector_type(2)));
 // check is on voffset, so rows past n (the SGPR offset) must use it too
 constexpr int kOOB = 0x7ffffff0;
 
-
 // The prefix of a MsgDesc the kernel reads (m … z), staged in LDS a block of plan entries at a time.
 struct alignas(16) ResMsg {
   int m, flags, parity, assoc_slot;
@@ -91,8 +107,546 @@ struct ResShared {
   double kw[W][RS][4];          // per wave: K[row(s)] (and Joseph: (Σ·Hᵀ)[row(s)]), wave-private
 };
 
+// One thread's share of the filter and of the plan walk's state.
+template <int W, int RS, int CS>
+struct ResState {
+  double sg[RS][CS];  // Σ[row(s)][col(t)]; indexed by compile-time constants only (registers)
+  // x and per-row scalars live lane-distributed: lane s < RS holds row w + W·s (its own row rl)
+  int lane, w, rl;
+  bool rown;
+  double xl = 0.0;
+  double tmo[3];
+  // posterior deferred to the next gather of the pose (the next message's predict gathers it
+  // anyway; nothing moves the pose in between): one barrier per message instead of two
+  bool post = false;
+  double podom[3] = {0.0, 0.0, 0.0};
+  unsigned counter = 0, status = 0;
+  unsigned long long dslots = 0;  // association slots decided in this launch (sh.decj/decn)
+  int par = -1;                   // current parity (−1: not loaded yet)
+  bool dirty = false;             // Σ / x changed (a chunk entry ran)
+  int b = 0;                      // gather buffer
+  // wq: the wave index re-materialised per correction (an opaque copy), so the compiler recomputes
+  // the per-row conditions in a few scalar ops instead of hoisting them out of the plan loop into
+  // (spilled) SGPRs
+  int wq;
+  int ncorr = 0;  // corrections so far (diagnostic stamps)
+
+  __device__ __forceinline__ int row(int s) const { return wq + W * s; }
+  __device__ __forceinline__ int col(int t) const { return lane + 64 * t; }
+  // x[r] ← v on the owner of row r
+  __device__ __forceinline__ void set_x(int r, double v) {
+    if (rown && rl == r) xl = v;
+  }
+};
+
 __device__ __forceinline__ int pos5(int r, int j) {
   return r < 3 ? r : (r == j ? 3 : (r == j + 1 ? 4 : -1));
+}
+
+// (o0, o1) = Σ_a (H0[a], H1[a])·v(a), a over {θ, x, y, jx, jy}, in that order: a column of H·Σ
+// from gathered rows, a row of Σ·Hᵀ from gathered columns
+template <typename V>
+__device__ __forceinline__ void times_H(const double* H0, const double* H1, const V& v, double& o0,
+                                        double& o1) {
+  o0 = 0.0;
+  o1 = 0.0;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const double va = v(a);
+    o0 += H0[a] * va;
+    o1 += H1[a] * va;
+  }
+}
+
+// K = q·S⁻¹ for one row q of Σ·Hᵀ
+__device__ __forceinline__ void gain(double q0, double q1, const double* Si, double& K0,
+                                     double& K1) {
+  K0 = q0 * Si[0] + q1 * Si[2];
+  K1 = q0 * Si[1] + q1 * Si[3];
+}
+
+// A first sighting's landmark position from the pose and the measurement (slam.cpp:213-216,
+// :351-356)
+__device__ __forceinline__ void landmark_from(double th, double px, double py, double z0, double z1,
+                                              double& lx, double& ly) {
+  double sn, cs;
+  sincos(z1 + th, &sn, &cs);
+  lx = px + z0 * cs;
+  ly = py + z0 * sn;
+}
+
+// Stage the block's descriptors: every thread fetches 16-byte pieces (plan entry → descriptor,
+// one dependent pair of loads per thread, all in flight together), one barrier. Returns the
+// number of entries staged.
+template <int W, int RS, int CS>
+__device__ __forceinline__ int stage_plan_block(ResShared<W, RS, CS>& sh, const MsgDesc* desc,
+                                                const PlanEntry* plan, int nplan, int l0, int f) {
+  const int nb = min(kBlk, nplan - l0);
+  __syncthreads();  // the previous block's entries are consumed
+  for (int t = threadIdx.x; t < nb * kMsgQ; t += W * 64) {
+    const int e = t / kMsgQ, q = t - e * kMsgQ;
+    const PlanEntry L = plan[l0 + e];
+    const bool mine = f >= L.f0 && f < L.f0 + L.nf;
+    if (q == 0) sh.kind[e] = mine ? L.kind : -1;
+    if (mine)
+      reinterpret_cast<uint4*>(&sh.msg[e])[q] =
+          reinterpret_cast<const uint4*>(desc + L.off + (f - L.f0))[q];
+  }
+  __syncthreads();
+  return nb;
+}
+
+// Σ and x of parity par into registers, t_map_odom and the counter from the filter's control block
+template <int W, int RS, int CS>
+__device__ __forceinline__ void load_filter(ResState<W, RS, CS>& st, const PassArgs<double>& A,
+                                            const FilterCtl* ctl, int f, int par) {
+  const int n = A.n, ld = A.ld;
+  st.par = par;
+  const double* S = A.sig[par] + f * A.sig_stride;
+  const double* X = A.x[par] + f * A.x_stride;
+  // buffer loads: row offset in the SGPR operand, column in the VGPR one; out-of-range
+  // rows / columns read 0 (the descriptor covers exactly n rows)
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(S), 0, n * ld * 8, 0x00020000);
+#pragma unroll
+  for (int s = 0; s < RS; ++s) {
+    const int r = st.row(s);
+#pragma unroll
+    for (int t = 0; t < CS; ++t) {
+      const int c = st.col(t);
+      const double v = __builtin_bit_cast(
+          double, __builtin_amdgcn_raw_buffer_load_b64(rs, r < n && c < n ? c * 8 : kOOB, r * ld * 8, 0));
+      st.sg[s][t] = (r < n && c < n) ? v : 0.0;
+    }
+  }
+  st.xl = (st.rown && st.rl < n) ? X[st.rl] : 0.0;
+  st.tmo[0] = ctl->tmo[0];
+  st.tmo[1] = ctl->tmo[1];
+  st.tmo[2] = ctl->tmo[2];
+  st.counter = ctl->counter;
+}
+
+// Rows / columns idx_a with a ≥ amin (j < 0: pose only) and their x into gather buffer bb
+template <int W, int RS, int CS>
+__device__ __forceinline__ void gather_rows(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                            int n, int bb, int j, int amin) {
+  asm volatile("" : "+s"(st.wq));
+  // rows: θ, x, y are slot 0 of waves 0-2; jx, jy sit in slot r / W of wave r % W, picked by
+  // one jump-table switch each (a few scalar ops and one indirect branch: the scalar unit is
+  // shared by the CU's waves, a test per slot costs more; a run-time index into sg would send
+  // the array to scratch)
+  if (amin == 0 && st.wq < 3) {
+#pragma unroll
+    for (int t = 0; t < CS; ++t) sh.grow[bb][st.wq][st.col(t)] = st.sg[0][t];
+  }
+  // The switch picks among values, not among loads through st: this function is optimised on
+  // its own before it is inlined, and there the cases' loads st.sg[q][t] merge into one load of
+  // a selected address, which keeps that column of Σ in scratch. The copy vanishes once inlined.
+  double v[RS][CS];
+#pragma unroll
+  for (int s = 0; s < RS; ++s)
+#pragma unroll
+    for (int t = 0; t < CS; ++t) v[s][t] = st.sg[s][t];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
+    const int r = j + e;
+    if (j >= 0 && r < n && r % W == st.wq) {
+      double* dst = &sh.grow[bb][3 + e][0];
+      switch (r / W) {
+#define RES_SLOT(q)                                                                \
+  case q:                                                                          \
+    if constexpr (q < RS) {                                                        \
+      _Pragma("unroll") for (int t = 0; t < CS; ++t) dst[st.col(t)] = v[q][t];     \
+    }                                                                              \
+    break;
+#define RES_SLOT8(q) RES_SLOT(q) RES_SLOT(q + 1) RES_SLOT(q + 2) RES_SLOT(q + 3) \
+    RES_SLOT(q + 4) RES_SLOT(q + 5) RES_SLOT(q + 6) RES_SLOT(q + 7)
+        RES_SLOT8(0) RES_SLOT8(8) RES_SLOT8(16) RES_SLOT8(24)
+#undef RES_SLOT8
+#undef RES_SLOT
+        default:
+          break;
+      }
+    }
+  }
+  {
+    const int a = pos5(st.rl, j);
+    if (st.rown && a >= amin && st.rl < n) sh.gx[bb][a] = st.xl;
+  }
+#pragma unroll
+  for (int t = 0; t < CS; ++t) {
+    const int c = st.col(t), a = pos5(c, j);
+    if (a >= amin && c < n) {
+#pragma unroll
+      for (int s = 0; s < RS; ++s) sh.gcol[bb][a][st.row(s)] = st.sg[s][t];
+    }
+  }
+}
+
+// posterior t_map_odom = T(x, y, θ)·t_odom_robot⁻¹ (slam.cpp:273-291) from a gathered pose
+template <int W, int RS, int CS>
+__device__ __forceinline__ void posterior_from(ResState<W, RS, CS>& st, double p0, double p1,
+                                               double p2) {
+  const Pose2 t = compose_sc(Pose2{p0, p1, p2},
+                             inverse_sc(Pose2{st.podom[0], st.podom[1], st.podom[2]}));
+  st.tmo[0] = t.theta;
+  st.tmo[1] = t.x;
+  st.tmo[2] = t.y;
+  st.post = false;
+}
+template <int W, int RS, int CS>
+__device__ __forceinline__ void posterior_now(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh) {
+  st.b ^= 1;
+  if (st.rown && st.rl < 3) sh.gx[st.b][st.rl] = st.xl;
+  __syncthreads();
+  posterior_from(st, sh.gx[st.b][0], sh.gx[st.b][1], sh.gx[st.b][2]);
+}
+
+// predict, slam.cpp:184-198: Σ = AΣAᵀ + Q̄, A = I + α·e0ᵀ; the last message's deferred posterior
+// rides on its pose gather
+template <int W, int RS, int CS>
+__device__ __forceinline__ void predict(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh, int n,
+                                        double q, const double* odom) {
+  st.b ^= 1;
+  const int b = st.b;
+  gather_rows(st, sh, n, b, -8, 0);
+  __syncthreads();
+  const double prev[3] = {sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]};
+  if (st.post) posterior_from(st, prev[0], prev[1], prev[2]);
+  const Pose2 cur = compose_sc(Pose2{st.tmo[0], st.tmo[1], st.tmo[2]},
+                               Pose2{odom[0], odom[1], odom[2]});
+  const double a1 = -(cur.y - prev[2]), a2 = cur.x - prev[1];
+  const double s00 = sh.grow[b][0][0];
+#pragma unroll
+  for (int s = 0; s < RS; ++s) {
+    const int r = st.row(s);
+    const double aa = alpha_of(r, a1, a2);
+    const double cr0 = sh.gcol[b][0][r];  // Σ[r][0], broadcast
+#pragma unroll
+    for (int t = 0; t < CS; ++t) {
+      const int c = st.col(t);
+      const double ab = alpha_of(c, a1, a2);
+      double v = st.sg[s][t] + aa * sh.grow[b][0][c];
+      v = v + (cr0 + aa * s00) * ab;
+      if (r == c && r < 3) v += q;
+      st.sg[s][t] = v;
+    }
+  }
+  st.set_x(0, normalize_angle(cur.theta));
+  st.set_x(1, cur.x);
+  st.set_x(2, cur.y);
+}
+
+// What a correction's update needs from its geometry: H, S, S⁻¹, ν, this lane's columns of
+// M = H·Σ and its row's gain
+template <int CS>
+struct Corr {
+  double H0[5], H1[5], Sm[4], Si[4], nv0, nv1, K0, K1;
+  double mc0[CS], mc1[CS];  // (H·Σ)[:, c] of this lane's columns
+};
+
+// ẑ, H, M, S, S⁻¹, ν and K of a correction against column j from gather buffer b; the wave's
+// rows' K (and Σ·Hᵀ) are left in its kw slots. false: S is singular (the marker is skipped).
+template <int W, int RS, int CS>
+__device__ __forceinline__ bool innovation_gain(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                                double r_noise, int j, double z0, double z1,
+                                                bool noinit, Corr<CS>& c) {
+  const int b = st.b;
+  const double pose[3] = {sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]};
+  double lx = sh.gx[b][3], ly = sh.gx[b][4];
+  if (!noinit && lx == 0.0 && ly == 0.0) {  // first sighting, slam.cpp:213-216
+    landmark_from(pose[0], pose[1], pose[2], z0, z1, lx, ly);
+    st.set_x(j, lx);
+    st.set_x(j + 1, ly);
+  }
+  double zhat[2], braw;
+  bool bok;
+  range_bearing(pose, lx, ly, zhat, c.H0, c.H1, &braw, &bok);
+  if (!bok) zhat[1] = normalize_angle(braw);
+  RS_STAMP(st.ncorr, 2);
+#pragma unroll
+  for (int t = 0; t < CS; ++t)
+    times_H(c.H0, c.H1, [&](int a) { return sh.grow[b][a][st.col(t)]; }, c.mc0[t], c.mc1[t]);
+  // S = (H·Σ)[:, idx]·Hᵀ + R (slam.cpp:252, left to right like arma); (H·Σ)[:, idx] from the
+  // lanes that own those columns
+  c.Sm[0] = c.Sm[1] = c.Sm[2] = c.Sm[3] = 0.0;
+#pragma unroll
+  for (int bb = 0; bb < 5; ++bb) {
+    const int cc = bb < 3 ? bb : j + bb - 3;
+    double v0 = c.mc0[0], v1 = c.mc1[0];
+#pragma unroll
+    for (int t = 1; t < CS; ++t)
+      if ((cc >> 6) == t) {
+        v0 = c.mc0[t];
+        v1 = c.mc1[t];
+      }
+    const double h0 = readlane_f64(v0, cc & 63), h1 = readlane_f64(v1, cc & 63);
+    c.Sm[0] += h0 * c.H0[bb];
+    c.Sm[1] += h0 * c.H1[bb];
+    c.Sm[2] += h1 * c.H0[bb];
+    c.Sm[3] += h1 * c.H1[bb];
+  }
+  c.Sm[0] += r_noise;
+  c.Sm[3] += r_noise;
+  if (!inv2(c.Sm, c.Si)) return false;  // arma::inv throws in the reference
+  c.nv0 = range_innovation(pose, lx, ly, z0);
+  bool nok;
+  const double nn = normalize_angle_near(z1 - zhat[1], &nok);
+  c.nv1 = nok ? nn : normalize_angle(z1 - zhat[1]);
+  RS_STAMP(st.ncorr, 3);
+  // K[rl] = (Σ·Hᵀ)[rl]·S⁻¹ on the lane that holds row rl, then every lane takes its rows' K
+  double ka, kb;
+  times_H(c.H0, c.H1, [&](int a) { return sh.gcol[b][a][st.rl]; }, ka, kb);
+  gain(ka, kb, c.Si, c.K0, c.K1);
+  // the wave's rows' K through its own LDS slots (one wave: LDS ops complete in issue order)
+  if (st.rown) {
+    sh.kw[st.w][st.lane][0] = c.K0;
+    sh.kw[st.w][st.lane][1] = c.K1;
+    sh.kw[st.w][st.lane][2] = ka;
+    sh.kw[st.w][st.lane][3] = kb;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return true;
+}
+
+// Σ ← Σ − K·(HΣ), slam.cpp:264-265
+template <int W, int RS, int CS>
+__device__ __forceinline__ void apply_simple(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                             const Corr<CS>& c) {
+#pragma unroll
+  for (int s = 0; s < RS; ++s) {
+    const double k0 = sh.kw[st.w][s][0], k1 = sh.kw[st.w][s][1];  // broadcast reads
+#pragma unroll
+    for (int t = 0; t < CS; ++t)
+      st.sg[s][t] = fma(-k1, c.mc1[t], fma(-k0, c.mc0[t], st.sg[s][t]));
+  }
+}
+
+// Joseph form (opt-in): Σ ← (I−KH)Σ(I−KH)ᵀ + KRKᵀ = Σ − K·(HΣ) − (ΣHᵀ)·Kᵀ + K·S·Kᵀ. Per
+// column c: K[c] from (ΣHᵀ)[c] (the gathered columns at row c) and u = S·K[c]ᵀ; then each
+// element takes Σ_rc − K_r·(M_c − u_c) − (ΣHᵀ)_r·K_cᵀ, four FMAs
+template <int W, int RS, int CS>
+__device__ __forceinline__ void apply_joseph(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                             Corr<CS>& c) {
+  const int b = st.b;
+  double kc0[CS], kc1[CS];
+#pragma unroll
+  for (int t = 0; t < CS; ++t) {
+    const int cc = min(st.col(t), W * RS - 1);  // columns ≥ n: never stored
+    double pa, pb;
+    times_H(c.H0, c.H1, [&](int a) { return sh.gcol[b][a][cc]; }, pa, pb);
+    gain(pa, pb, c.Si, kc0[t], kc1[t]);
+    c.mc0[t] -= c.Sm[0] * kc0[t] + c.Sm[1] * kc1[t];
+    c.mc1[t] -= c.Sm[2] * kc0[t] + c.Sm[3] * kc1[t];
+  }
+#pragma unroll
+  for (int s = 0; s < RS; ++s) {
+    const double k0 = sh.kw[st.w][s][0], k1 = sh.kw[st.w][s][1];
+    const double p0 = sh.kw[st.w][s][2], p1 = sh.kw[st.w][s][3];
+#pragma unroll
+    for (int t = 0; t < CS; ++t)
+      st.sg[s][t] = fma(-p1, kc1[t], fma(-p0, kc0[t],
+                        fma(-k1, c.mc1[t], fma(-k0, c.mc0[t], st.sg[s][t]))));
+  }
+}
+
+// One correction against landmark column j = 3 + 2·id (slam.cpp:219-267 / :443-488). The
+// gather of idx into buffer b is done and the barrier passed.
+template <int W, int RS, int CS, bool JOSEPH>
+__device__ __forceinline__ void correct(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                        double r_noise, int j, double z0, double z1, bool noinit) {
+  RS_STAMP(st.ncorr, 1);
+  asm volatile("" : "+s"(st.wq));
+  Corr<CS> c;
+  if (!innovation_gain(st, sh, r_noise, j, z0, z1, noinit, c)) {  // skip the marker, flag it
+    st.status |= EKF_FLAG_NUMERIC_D;
+    return;
+  }
+  // x's increment first (it reads nothing the Σ update writes): K and ν are then dead across the
+  // update, which is where the Joseph kernels run out of registers
+  double xt = st.xl + (c.K0 * c.nv0 + c.K1 * c.nv1);  // slam.cpp:261
+  if constexpr (JOSEPH)
+    apply_joseph(st, sh, c);
+  else
+    apply_simple(st, sh, c);
+  if (st.rl == 0) {                                    // slam.cpp:267
+    bool tok;
+    const double tn = normalize_angle_near(xt, &tok);
+    xt = tok ? tn : normalize_angle(xt);
+  }
+  st.xl = xt;
+  RS_STAMP(st.ncorr, 4);
+  ++st.ncorr;
+}
+
+// Landmark 2×2 blocks of the seen landmarks (rows < 3 + 2·counter) and x for the scoring wave:
+// every (slot, column) element stores — to its block entry when it is one, else to this lane's
+// junk slot. The row index is taken as a vector value (tid >> 6 unmerged), so the index math
+// runs on each SIMD's VALU, not on the CU's one scalar unit.
+template <int W, int RS, int CS>
+__device__ __forceinline__ void gather_assoc_blocks(ResState<W, RS, CS>& st,
+                                                    ResShared<W, RS, CS>& sh, int n) {
+  const int wv = static_cast<int>(threadIdx.x) >> 6;
+  const int rmax = 3 + 2 * static_cast<int>(st.counter);
+#pragma unroll
+  for (int s = 0; s < RS; ++s) {
+    if (st.row(s) >= rmax) break;  // rows grow with s
+    const int r = wv + W * s;
+    const int k = (r - 3) >> 1, e = (r - 3) & 1;
+#pragma unroll
+    for (int t = 0; t < CS; ++t) {
+      const int dc = st.col(t) - (3 + 2 * k);
+      const bool in = r >= 3 && (dc == 0 || dc == 1);
+      *(in ? &sh.blk[k < 0 ? 0 : k][2 * e + dc] : &sh.junk[st.lane]) = st.sg[s][t];
+    }
+  }
+  if (st.rown && st.rl >= 3 && st.rl < n) sh.xall[st.rl] = st.xl;
+}
+
+// Wave 0: lane k scores landmark k (k + 64, …) against the marker, the wave takes the argmin and
+// lane 0 decides between it and a new landmark at slot counter (slam.cpp:361-422)
+template <int W, int RS, int CS>
+__device__ __forceinline__ void score_and_decide(const ResState<W, RS, CS>& st,
+                                                 ResShared<W, RS, CS>& sh, double r_noise,
+                                                 double gate, double z0, double z1, int slot) {
+  const int b = st.b;
+  const double pose[3] = {sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]};
+  double bestd = INFINITY;
+  int bestk = INT_MAX;
+  for (unsigned k = st.lane; k < st.counter; k += 64) {
+    const int j = 3 + 2 * static_cast<int>(k);
+    // Σ over {θ, x, y, j, j+1}, read where it is used
+    auto P = [&](int a, int c) __attribute__((always_inline)) -> double {
+      if (a < 3) return sh.grow[b][a][c < 3 ? c : j + c - 3];
+      if (c < 3) return sh.gcol[b][c][j + a - 3];
+      return sh.blk[k][2 * (a - 3) + (c - 3)];
+    };
+    // assoc_dist's expression (ekf_math.hpp) with Σ read through P; kept apart from it because
+    // this kernel has always rounded ẑ_range before the subtraction, where k_assoc and
+    // k_assoc_msg contract the two: one shared form cannot keep all three bit for bit
+    double zhat[2], H0[5], H1[5], braw;
+    bool bok;
+    range_bearing(pose, sh.xall[j], sh.xall[j + 1], zhat, H0, H1, &braw, &bok);
+    if (!bok) zhat[1] = normalize_angle(braw);
+    double psi[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int bb = 0; bb < 5; ++bb) {
+      double hp0, hp1;  // (H·P)[:, bb]
+      times_H(H0, H1, [&](int a) { return P(a, bb); }, hp0, hp1);
+      psi[0] += hp0 * H0[bb];
+      psi[1] += hp0 * H1[bb];
+      psi[2] += hp1 * H0[bb];
+      psi[3] += hp1 * H1[bb];
+    }
+    psi[0] += r_noise;
+    psi[3] += r_noise;
+    const double nu0 = sub_rounded(z0, zhat[0]);
+    const double nu1 = normalize_angle(z1 - zhat[1]);
+    double dist = NAN;
+    const double det = psi[0] * psi[3] - psi[1] * psi[2];
+    if (fabs(det) > 0.0) {  // (z_diffᵀ·ψ⁻¹)·z_diff, slam.cpp:401
+      const double t0 = nu0 * psi[3] - nu1 * psi[2];
+      const double t1 = nu1 * psi[0] - nu0 * psi[1];
+      dist = (t0 * nu0 + t1 * nu1) / det;
+    }
+    if (dist < bestd) {  // strict: first index kept, NaN never selected
+      bestd = dist;
+      bestk = static_cast<int>(k);
+    }
+  }
+  wave_argmin(bestd, bestk);  // (DPP, ekf_math.hpp; every lane holds the result)
+  if (st.lane == 0) {
+    // the new slot (d = gate, slam.cpp:406-408) wins only over a larger minimum
+    const bool nw = !(bestd <= gate);
+    const int jsel = nw ? static_cast<int>(st.counter) : bestk;
+    sh.dec[0] = jsel;
+    sh.dec[1] = nw;
+    sh.decj[slot] = jsel;
+    sh.decn[slot] = nw;
+  }
+}
+
+// A new landmark at column j from the pose in gather buffer b (slam.cpp:351-356, kept: :421)
+template <int W, int RS, int CS>
+__device__ __forceinline__ void init_new_landmark(ResState<W, RS, CS>& st,
+                                                  ResShared<W, RS, CS>& sh, int j, double z0,
+                                                  double z1) {
+  double lx, ly;
+  landmark_from(sh.gx[st.b][0], sh.gx[st.b][1], sh.gx[st.b][2], z0, z1, lx, ly);
+  st.set_x(j, lx);
+  st.set_x(j + 1, ly);
+  ++st.counter;
+}
+
+// Association + correction of one marker, slam.cpp:344-488
+template <int W, int RS, int CS, bool JOSEPH>
+__device__ __forceinline__ void associate_correct(ResState<W, RS, CS>& st,
+                                                  ResShared<W, RS, CS>& sh,
+                                                  const PassArgs<double>& A, double z0, double z1,
+                                                  int slot) {
+  st.dslots |= 1ull << slot;
+  if (st.counter >= static_cast<unsigned>(A.N)) {  // the reference indexes out of range
+    st.status |= EKF_FLAG_RANGE_D;
+    if (threadIdx.x == 0) {
+      sh.decj[slot] = -1;
+      sh.decn[slot] = 0;
+    }
+    return;
+  }
+  RS_STAMP(st.ncorr, 0);
+  st.b ^= 1;
+  gather_rows(st, sh, A.n, st.b, -8, 0);  // pose rows / columns and pose x
+  gather_assoc_blocks(st, sh, A.n);
+  __syncthreads();
+  RS_STAMP(st.ncorr, 6);
+  if (st.w == 0) score_and_decide(st, sh, A.r, A.gate, z0, z1, slot);
+  __syncthreads();
+  const int j = 3 + 2 * sh.dec[0];
+  if (sh.dec[1]) init_new_landmark(st, sh, j, z0, z1);
+  RS_STAMP(st.ncorr, 7);
+  gather_rows(st, sh, A.n, st.b, j, 3);  // the pose rows / columns are in b already
+  RS_STAMP(st.ncorr, 5);
+  __syncthreads();
+  correct<W, RS, CS, JOSEPH>(st, sh, A.r, j, z0, z1, true);
+}
+
+// The decisions, Σ and x (when a chunk entry changed them, to parity par), t_map_odom, the
+// counter and the status flags
+template <int W, int RS, int CS>
+__device__ __forceinline__ void store_filter(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                             const PassArgs<double>& A, FilterCtl* ctl, int f) {
+  const int n = A.n, ld = A.ld, tid = threadIdx.x;
+  __syncthreads();  // the decisions in LDS
+  if (tid < kMaxAssoc && (st.dslots >> tid & 1)) {
+    ctl->assoc_j[tid] = sh.decj[tid];
+    ctl->assoc_new[tid] = sh.decn[tid];
+  }
+  if (st.dirty) {
+    double* S = A.sig[st.par] + f * A.sig_stride;
+    double* X = A.x[st.par] + f * A.x_stride;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(S, 0, n * ld * 8, 0x00020000);
+#pragma unroll
+    for (int s = 0; s < RS; ++s) {
+      const int r = st.row(s);
+      if (r >= n) continue;
+#pragma unroll
+      for (int t = 0; t < CS; ++t) {
+        const int c = st.col(t);  // columns ≥ n go out of the descriptor's range (dropped)
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, st.sg[s][t]), rs,
+                                              c < n ? c * 8 : kOOB, r * ld * 8, 0);
+      }
+    }
+    if (st.rown && st.rl < n) X[st.rl] = st.xl;
+  }
+  if (tid == 0) {
+    ctl->tmo[0] = st.tmo[0];
+    ctl->tmo[1] = st.tmo[1];
+    ctl->tmo[2] = st.tmo[2];
+    ctl->counter = st.counter;
+    if (st.status) atomicOr(&ctl->status, st.status);
+  }
 }
 
 }  // namespace
@@ -103,489 +657,59 @@ __device__ __forceinline__ int pos5(int r, int j) {
 template <int W, int RS, int CS, bool JOSEPH>
 __global__ __launch_bounds__(W * 64) void k_resident(PassArgs<double> A, const PlanEntry* plan,
                                                      int nplan, int flo) {
-  constexpr int kRW = W;
-  static_assert(RS <= 32 && RS <= 64, "jump-table gather covers 32 slots; x is lane-distributed");
+  static_assert(RS <= 32, "jump-table gather covers 32 slots; x is lane-distributed");
   __shared__ ResShared<W, RS, CS> sh;
   const int f = flo + blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: row offsets in SGPRs
-  const int n = A.n, ld = A.ld, N = A.N;
   FilterCtl* ctl = A.ctl + f;
-
-  double sg[RS][CS];
-  // x and per-row scalars live lane-distributed: lane s < RS holds row w + kRW·s (its own row rl)
-  const int rl = w + kRW * (lane < RS ? lane : RS - 1);
-  const bool rown = lane < RS;
-  double xl = 0.0;
-  double tmo[3];
-  // posterior deferred to the next gather of the pose (the next message's predict gathers it
-  // anyway; nothing moves the pose in between): one barrier per message instead of two
-  bool post = false;
-  double podom[3] = {0.0, 0.0, 0.0};
-  unsigned counter = 0, status = 0;
-  unsigned long long dslots = 0;  // association slots decided in this launch (sh.decj/decn)
-  int par = -1;          // current parity (−1: not loaded yet)
-  bool dirty = false;    // Σ / x changed (a chunk entry ran)
-  int b = 0;             // gather buffer
-
-  // wq: the wave index re-materialised per correction (an opaque copy), so the compiler recomputes
-  // the per-row conditions in a few scalar ops instead of hoisting them out of the plan loop into
-  // (spilled) SGPRs
-  int wq = w;
-  auto row = [&](int s) __attribute__((always_inline)) { return wq + kRW * s; };
-  auto col = [&](int t) __attribute__((always_inline)) { return lane + 64 * t; };
-
-  // rows / columns idx_a with a ≥ amin (j < 0: pose only) and their x into gather buffer bb
-  auto gather = [&](int bb, int j, int amin) __attribute__((always_inline)) {
-    asm volatile("" : "+s"(wq));
-    // rows: θ, x, y are slot 0 of waves 0-2; jx, jy sit in slot r / W of wave r % W, picked by
-    // one jump-table switch each (a few scalar ops and one indirect branch: the scalar unit is
-    // shared by the CU's waves, a test per slot costs more)
-    if (amin == 0 && wq < 3) {
-#pragma unroll
-      for (int t = 0; t < CS; ++t) sh.grow[bb][wq][col(t)] = sg[0][t];
-    }
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int r = j + e;
-      if (j >= 0 && r < n && r % kRW == wq) {
-        double* dst = &sh.grow[bb][3 + e][0];
-        switch (r / kRW) {
-#define RES_SLOT(q)                                                      \
-  case q:                                                                \
-    if constexpr (q < RS) {                                              \
-      _Pragma("unroll") for (int t = 0; t < CS; ++t) dst[col(t)] = sg[q][t]; \
-    }                                                                    \
-    break;
-          RES_SLOT(0) RES_SLOT(1) RES_SLOT(2) RES_SLOT(3) RES_SLOT(4) RES_SLOT(5) RES_SLOT(6)
-          RES_SLOT(7) RES_SLOT(8) RES_SLOT(9) RES_SLOT(10) RES_SLOT(11) RES_SLOT(12) RES_SLOT(13)
-          RES_SLOT(14) RES_SLOT(15) RES_SLOT(16) RES_SLOT(17) RES_SLOT(18) RES_SLOT(19)
-          RES_SLOT(20) RES_SLOT(21) RES_SLOT(22) RES_SLOT(23) RES_SLOT(24) RES_SLOT(25)
-          RES_SLOT(26) RES_SLOT(27) RES_SLOT(28) RES_SLOT(29) RES_SLOT(30) RES_SLOT(31)
-#undef RES_SLOT
-          default:
-            break;
-        }
-      }
-    }
-    {
-      const int a = pos5(rl, j);
-      if (rown && a >= amin && rl < n) sh.gx[bb][a] = xl;
-    }
-#pragma unroll
-    for (int t = 0; t < CS; ++t) {
-      const int c = col(t), a = pos5(c, j);
-      if (a >= amin && c < n) {
-#pragma unroll
-        for (int s = 0; s < RS; ++s) sh.gcol[bb][a][row(s)] = sg[s][t];
-      }
-    }
-  };
-  // x[r] ← v on the owner of row r
-  auto set_x = [&](int r, double v) __attribute__((always_inline)) {
-    if (rown && rl == r) xl = v;
-  };
-
-  // One correction against landmark column j = 3 + 2·id (slam.cpp:219-267 / :443-488). The
-  // gather of idx into buffer b is done and the barrier passed.
-  // posterior t_map_odom = T(x, y, θ)·t_odom_robot⁻¹ (slam.cpp:273-291) from a gathered pose
-  auto posterior_from = [&](double p0, double p1, double p2) __attribute__((always_inline)) {
-    const Pose2 t = compose_sc(Pose2{p0, p1, p2}, inverse_sc(Pose2{podom[0], podom[1], podom[2]}));
-    tmo[0] = t.theta;
-    tmo[1] = t.x;
-    tmo[2] = t.y;
-    post = false;
-  };
-  auto posterior_now = [&]() __attribute__((always_inline)) {
-    b ^= 1;
-    if (rown && rl < 3) sh.gx[b][rl] = xl;
-    __syncthreads();
-    posterior_from(sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]);
-  };
-  [[maybe_unused]] int ncorr = 0;  // corrections so far (diagnostic stamps)
-  auto correct = [&](int j, double z0, double z1, bool noinit) __attribute__((always_inline)) {
-    RS_STAMP(ncorr, 1);
-    asm volatile("" : "+s"(wq));
-    const double pose[3] = {sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]};
-    double lx = sh.gx[b][3], ly = sh.gx[b][4];
-    if (!noinit && lx == 0.0 && ly == 0.0) {  // first sighting, slam.cpp:213-216
-      double sn, cs;
-      sincos(z1 + pose[0], &sn, &cs);
-      lx = pose[1] + z0 * cs;
-      ly = pose[2] + z0 * sn;
-      set_x(j, lx);
-      set_x(j + 1, ly);
-    }
-    double zhat[2], H0[5], H1[5], braw;
-    bool bok;
-    range_bearing(pose, lx, ly, zhat, H0, H1, &braw, &bok);
-    if (!bok) zhat[1] = normalize_angle(braw);
-    RS_STAMP(ncorr, 2);
-    double mc0[CS], mc1[CS];  // (H·Σ)[:, c] of this lane's columns
-#pragma unroll
-    for (int t = 0; t < CS; ++t) {
-      double m0 = 0.0, m1 = 0.0;
-#pragma unroll
-      for (int a = 0; a < 5; ++a) {
-        const double v = sh.grow[b][a][col(t)];
-        m0 += H0[a] * v;
-        m1 += H1[a] * v;
-      }
-      mc0[t] = m0;
-      mc1[t] = m1;
-    }
-    // S = (H·Σ)[:, idx]·Hᵀ + R (slam.cpp:252, left to right like arma); (H·Σ)[:, idx] from the
-    // lanes that own those columns
-    double Sm[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int bb = 0; bb < 5; ++bb) {
-      const int c = bb < 3 ? bb : j + bb - 3;
-      double v0 = mc0[0], v1 = mc1[0];
-#pragma unroll
-      for (int t = 1; t < CS; ++t)
-        if ((c >> 6) == t) {
-          v0 = mc0[t];
-          v1 = mc1[t];
-        }
-      const double h0 = readlane_f64(v0, c & 63), h1 = readlane_f64(v1, c & 63);
-      Sm[0] += h0 * H0[bb];
-      Sm[1] += h0 * H1[bb];
-      Sm[2] += h1 * H0[bb];
-      Sm[3] += h1 * H1[bb];
-    }
-    Sm[0] += A.r;
-    Sm[3] += A.r;
-    double Si[4];
-    if (!inv2(Sm, Si)) {  // arma::inv throws in the reference: skip the marker, flag it
-      status |= EKF_FLAG_NUMERIC_D;
-      return;
-    }
-    const double nv0 = z0 - zhat[0];
-    bool nok;
-    const double nn = normalize_angle_near(z1 - zhat[1], &nok);
-    const double nv1 = nok ? nn : normalize_angle(z1 - zhat[1]);
-    RS_STAMP(ncorr, 3);
-    // K[rl] = (Σ·Hᵀ)[rl]·S⁻¹ on the lane that holds row rl, then every lane takes its rows' K
-    double K0, K1, ka = 0.0, kb = 0.0;
-    {
-#pragma unroll
-      for (int a = 0; a < 5; ++a) {
-        const double v = sh.gcol[b][a][rl];
-        ka += v * H0[a];
-        kb += v * H1[a];
-      }
-      K0 = ka * Si[0] + kb * Si[2];
-      K1 = ka * Si[1] + kb * Si[3];
-    }
-    // the wave's rows' K through its own LDS slots (one wave: LDS ops complete in issue order)
-    if (rown) {
-      sh.kw[w][lane][0] = K0;
-      sh.kw[w][lane][1] = K1;
-      sh.kw[w][lane][2] = ka;
-      sh.kw[w][lane][3] = kb;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if constexpr (!JOSEPH) {  // Σ ← Σ − K·(HΣ), slam.cpp:264-265
-#pragma unroll
-      for (int s = 0; s < RS; ++s) {
-        const double k0 = sh.kw[w][s][0], k1 = sh.kw[w][s][1];  // broadcast reads
-#pragma unroll
-        for (int t = 0; t < CS; ++t) sg[s][t] = fma(-k1, mc1[t], fma(-k0, mc0[t], sg[s][t]));
-      }
-    } else {
-      // Joseph form (opt-in): Σ ← (I−KH)Σ(I−KH)ᵀ + KRKᵀ = Σ − K·(HΣ) − (ΣHᵀ)·Kᵀ + K·S·Kᵀ. Per
-      // column c: K[c] from (ΣHᵀ)[c] (the gathered columns at row c) and u = S·K[c]ᵀ; then each
-      // element takes Σ_rc − K_r·(M_c − u_c) − (ΣHᵀ)_r·K_cᵀ, four FMAs
-      double kc0[CS], kc1[CS];
-#pragma unroll
-      for (int t = 0; t < CS; ++t) {
-        const int c = min(col(t), kRW * RS - 1);  // columns ≥ n: never stored
-        double pa = 0.0, pb = 0.0;
-#pragma unroll
-        for (int a = 0; a < 5; ++a) {
-          const double v = sh.gcol[b][a][c];
-          pa += v * H0[a];
-          pb += v * H1[a];
-        }
-        kc0[t] = pa * Si[0] + pb * Si[2];
-        kc1[t] = pa * Si[1] + pb * Si[3];
-        mc0[t] -= Sm[0] * kc0[t] + Sm[1] * kc1[t];
-        mc1[t] -= Sm[2] * kc0[t] + Sm[3] * kc1[t];
-      }
-#pragma unroll
-      for (int s = 0; s < RS; ++s) {
-        const double k0 = sh.kw[w][s][0], k1 = sh.kw[w][s][1];
-        const double p0 = sh.kw[w][s][2], p1 = sh.kw[w][s][3];
-#pragma unroll
-        for (int t = 0; t < CS; ++t)
-          sg[s][t] = fma(-p1, kc1[t], fma(-p0, kc0[t],
-                         fma(-k1, mc1[t], fma(-k0, mc0[t], sg[s][t]))));
-      }
-    }
-    double xt = xl + (K0 * nv0 + K1 * nv1);  // slam.cpp:261
-    if (rl == 0) {                            // slam.cpp:267
-      bool tok;
-      const double tn = normalize_angle_near(xt, &tok);
-      xt = tok ? tn : normalize_angle(xt);
-    }
-    xl = xt;
-    RS_STAMP(ncorr, 4);
-    ++ncorr;
-  };
+  ResState<W, RS, CS> st;
+  st.lane = threadIdx.x & 63;
+  st.w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: row offsets in SGPRs
+  st.wq = st.w;
+  st.rown = st.lane < RS;
+  st.rl = st.w + W * (st.rown ? st.lane : RS - 1);
 
   for (int l0 = 0; l0 < nplan; l0 += kBlk) {
-  // stage the block's descriptors: every thread fetches 16-byte pieces (plan entry → descriptor,
-  // one dependent pair of loads per thread, all in flight together), one barrier
-  const int nb = min(kBlk, nplan - l0);
-  __syncthreads();  // the previous block's entries are consumed
-  for (int t = tid; t < nb * kMsgQ; t += kRW * 64) {
-    const int e = t / kMsgQ, q = t - e * kMsgQ;
-    const PlanEntry L = plan[l0 + e];
-    const bool mine = f >= L.f0 && f < L.f0 + L.nf;
-    if (q == 0) sh.kind[e] = mine ? L.kind : -1;
-    if (mine)
-      reinterpret_cast<uint4*>(&sh.msg[e])[q] =
-          reinterpret_cast<const uint4*>(A.desc + L.off + (f - L.f0))[q];
-  }
-  __syncthreads();
-  for (int e = 0; e < nb; ++e) {
-    const int kind = sh.kind[e];
-    if (kind < 0) continue;
-    const ResMsg& d = sh.msg[e];
-    const int flags = d.flags;
-    if (!(flags & kActive)) continue;
-    const PlanEntry L{0, 0, 0, kind};
-    if (par < 0) {  // first entry naming this filter: load it
-      par = d.parity;
-      const double* S = A.sig[par] + f * A.sig_stride;
-      const double* X = A.x[par] + f * A.x_stride;
-      // buffer loads: row offset in the SGPR operand, column in the VGPR one; out-of-range
-      // rows / columns read 0 (the descriptor covers exactly n rows)
-      const __amdgpu_buffer_rsrc_t rs =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(S), 0, n * ld * 8, 0x00020000);
-#pragma unroll
-      for (int s = 0; s < RS; ++s) {
-        const int r = row(s);
-#pragma unroll
-        for (int t = 0; t < CS; ++t) {
-          const int c = col(t);
-          const double v = __builtin_bit_cast(
-              double, __builtin_amdgcn_raw_buffer_load_b64(rs, r < n && c < n ? c * 8 : kOOB, r * ld * 8, 0));
-          sg[s][t] = (r < n && c < n) ? v : 0.0;
+    const int nb = stage_plan_block(sh, A.desc, plan, nplan, l0, f);
+    for (int e = 0; e < nb; ++e) {
+      const int kind = sh.kind[e];
+      if (kind < 0) continue;
+      const ResMsg& d = sh.msg[e];
+      const int flags = d.flags;
+      if (!(flags & kActive)) continue;
+      if (st.par < 0) load_filter(st, A, ctl, f, d.parity);  // first entry naming this filter
+      if (st.post && kind != kLaunchPosterior && !(flags & kFirst))
+        posterior_now(st, sh);  // corrections follow
+      if (kind != kLaunchPosterior) {
+        if (flags & kFirst) predict(st, sh, A.n, A.q, d.odom);
+        if (kind == kLaunchKnown) {  // known association, slam.cpp:201-271
+          for (int c = 0; c < d.m; ++c) {
+            const int id = d.ids[c];
+            if (id < 0 || id >= A.N) continue;  // validated on the host; never reached
+            RS_STAMP(st.ncorr, 0);
+            st.b ^= 1;
+            gather_rows(st, sh, A.n, st.b, 3 + 2 * id, 0);
+            RS_STAMP(st.ncorr, 5);
+            __syncthreads();
+            correct<W, RS, CS, JOSEPH>(st, sh, A.r, 3 + 2 * id, d.z[c][0], d.z[c][1],
+                                       (flags & kNoInit) != 0);
+          }
+        } else if (d.m > 0) {
+          associate_correct<W, RS, CS, JOSEPH>(st, sh, A, d.z[0][0], d.z[0][1], d.assoc_slot);
         }
+        st.par ^= 1;
+        st.dirty = true;
       }
-      xl = (rown && rl < n) ? X[rl] : 0.0;
-      tmo[0] = ctl->tmo[0];
-      tmo[1] = ctl->tmo[1];
-      tmo[2] = ctl->tmo[2];
-      counter = ctl->counter;
-    }
-    if (post && L.kind != kLaunchPosterior && !(flags & kFirst)) posterior_now();  // corrections follow
-    if (L.kind != kLaunchPosterior) {
-      if (flags & kFirst) {  // predict, slam.cpp:184-198: Σ = AΣAᵀ + Q̄, A = I + α·e0ᵀ
-        b ^= 1;
-        gather(b, -8, 0);
-        __syncthreads();
-        const double prev[3] = {sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]};
-        if (post) posterior_from(prev[0], prev[1], prev[2]);  // the last message's posterior
-        const Pose2 cur = compose_sc(Pose2{tmo[0], tmo[1], tmo[2]},
-                                     Pose2{d.odom[0], d.odom[1], d.odom[2]});
-        const double a1 = -(cur.y - prev[2]), a2 = cur.x - prev[1];
-        const double s00 = sh.grow[b][0][0];
-#pragma unroll
-        for (int s = 0; s < RS; ++s) {
-          const int r = row(s);
-          const double aa = alpha_of(r, a1, a2);
-          const double cr0 = sh.gcol[b][0][r];  // Σ[r][0], broadcast
-#pragma unroll
-          for (int t = 0; t < CS; ++t) {
-            const int c = col(t);
-            const double ab = alpha_of(c, a1, a2);
-            double v = sg[s][t] + aa * sh.grow[b][0][c];
-            v = v + (cr0 + aa * s00) * ab;
-            if (r == c && r < 3) v += A.q;
-            sg[s][t] = v;
-          }
-        }
-        set_x(0, normalize_angle(cur.theta));
-        set_x(1, cur.x);
-        set_x(2, cur.y);
-      }
-      if (L.kind == kLaunchKnown) {  // known association, slam.cpp:201-271
-        for (int c = 0; c < d.m; ++c) {
-          const int id = d.ids[c];
-          if (id < 0 || id >= N) continue;  // validated on the host; never reached
-          RS_STAMP(ncorr, 0);
-          b ^= 1;
-          gather(b, 3 + 2 * id, 0);
-          RS_STAMP(ncorr, 5);
-          __syncthreads();
-          correct(3 + 2 * id, d.z[c][0], d.z[c][1], (flags & kNoInit) != 0);
-        }
-      } else if (d.m > 0) {  // association + correction, slam.cpp:344-488
-        const double z0 = d.z[0][0], z1 = d.z[0][1];
-        const int slot = d.assoc_slot;
-        if (counter >= static_cast<unsigned>(N)) {  // the reference indexes out of range
-          status |= EKF_FLAG_RANGE_D;
-          if (tid == 0) {
-            sh.decj[slot] = -1;
-            sh.decn[slot] = 0;
-          }
-          dslots |= 1ull << slot;
-        } else {
-          RS_STAMP(ncorr, 0);
-          b ^= 1;
-          gather(b, -8, 0);  // pose rows / columns and pose x
-          // landmark 2×2 blocks of the seen landmarks (rows < 3 + 2·counter): every (slot,
-          // column) element stores — to its block entry when it is one, else to this lane's junk
-          // slot. The row index is taken as a vector value (tid >> 6 unmerged), so the index
-          // math runs on each SIMD's VALU, not on the CU's one scalar unit.
-          {
-            const int wv = static_cast<int>(threadIdx.x) >> 6;
-            const int rmax = 3 + 2 * static_cast<int>(counter);
-#pragma unroll
-            for (int s = 0; s < RS; ++s) {
-              if (row(s) >= rmax) break;  // rows grow with s
-              const int r = wv + kRW * s;
-              const int k = (r - 3) >> 1, e = (r - 3) & 1;
-#pragma unroll
-              for (int t = 0; t < CS; ++t) {
-                const int dc = col(t) - (3 + 2 * k);
-                const bool in = r >= 3 && (dc == 0 || dc == 1);
-                *(in ? &sh.blk[k < 0 ? 0 : k][2 * e + dc] : &sh.junk[lane]) = sg[s][t];
-              }
-            }
-          }
-          if (rown && rl >= 3 && rl < n) sh.xall[rl] = xl;
-          __syncthreads();
-          RS_STAMP(ncorr, 6);
-          if (w == 0) {
-            const double pose[3] = {sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]};
-            double bestd = INFINITY;
-            int bestk = INT_MAX;
-            for (unsigned k = lane; k < counter; k += 64) {
-              const int j = 3 + 2 * static_cast<int>(k);
-              // Σ over {θ, x, y, j, j+1}, read where it is used
-              auto P = [&](int a, int c) __attribute__((always_inline)) -> double {
-                if (a < 3) return sh.grow[b][a][c < 3 ? c : j + c - 3];
-                if (c < 3) return sh.gcol[b][c][j + a - 3];
-                return sh.blk[k][2 * (a - 3) + (c - 3)];
-              };
-              double zhat[2], H0[5], H1[5], braw;
-              bool bok;
-              range_bearing(pose, sh.xall[j], sh.xall[j + 1], zhat, H0, H1, &braw, &bok);
-              if (!bok) zhat[1] = normalize_angle(braw);
-              double HP0[5], HP1[5];
-#pragma unroll
-              for (int bb = 0; bb < 5; ++bb) {
-                double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                for (int a = 0; a < 5; ++a) {
-                  const double v = P(a, bb);
-                  s0 += H0[a] * v;
-                  s1 += H1[a] * v;
-                }
-                HP0[bb] = s0;
-                HP1[bb] = s1;
-              }
-              double psi[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-              for (int bb = 0; bb < 5; ++bb) {
-                psi[0] += HP0[bb] * H0[bb];
-                psi[1] += HP0[bb] * H1[bb];
-                psi[2] += HP1[bb] * H0[bb];
-                psi[3] += HP1[bb] * H1[bb];
-              }
-              psi[0] += A.r;
-              psi[3] += A.r;
-              const double nu0 = z0 - zhat[0];
-              const double nu1 = normalize_angle(z1 - zhat[1]);
-              double dist = NAN;
-              const double det = psi[0] * psi[3] - psi[1] * psi[2];
-              if (fabs(det) > 0.0) {  // (z_diffᵀ·ψ⁻¹)·z_diff, slam.cpp:401 (assoc_dist's form)
-                const double t0 = nu0 * psi[3] - nu1 * psi[2];
-                const double t1 = nu1 * psi[0] - nu0 * psi[1];
-                dist = (t0 * nu0 + t1 * nu1) / det;
-              }
-              if (dist < bestd) {  // strict: first index kept, NaN never selected
-                bestd = dist;
-                bestk = static_cast<int>(k);
-              }
-            }
-            wave_argmin(bestd, bestk);  // (DPP, ekf_math.hpp; every lane holds the result)
-            if (lane == 0) {
-              // the new slot (d = gate, slam.cpp:406-408) wins only over a larger minimum
-              const bool nw = !(bestd <= A.gate);
-              const int jsel = nw ? static_cast<int>(counter) : bestk;
-              sh.dec[0] = jsel;
-              sh.dec[1] = nw;
-              sh.decj[slot] = jsel;
-              sh.decn[slot] = nw;
-            }
-          }
-          __syncthreads();
-          dslots |= 1ull << slot;
-          const int k = sh.dec[0];
-          const int j = 3 + 2 * k;
-          if (sh.dec[1]) {  // slam.cpp:351-356, kept (:421)
-            const double p0 = sh.gx[b][0], p1 = sh.gx[b][1], p2 = sh.gx[b][2];
-            double sn, cs;
-            sincos(z1 + p0, &sn, &cs);
-            set_x(j, p1 + z0 * cs);
-            set_x(j + 1, p2 + z0 * sn);
-            ++counter;
-          }
-          RS_STAMP(ncorr, 7);
-          gather(b, j, 3);  // the pose rows / columns are in b already
-          RS_STAMP(ncorr, 5);
-          __syncthreads();
-          correct(j, z0, z1, true);
-        }
-      }
-      par ^= 1;
-      dirty = true;
-    }
-    if ((flags & kLast) || L.kind == kLaunchPosterior) {  // posterior, slam.cpp:273-291 (deferred)
-      post = true;
-      podom[0] = d.odom[0];
-      podom[1] = d.odom[1];
-      podom[2] = d.odom[2];
-    }
-  }
-  }
-  if (par < 0) return;  // the plan does not name this filter
-  if (post) posterior_now();
-  __syncthreads();  // the decisions in LDS
-  if (tid < kMaxAssoc && (dslots >> tid & 1)) {
-    ctl->assoc_j[tid] = sh.decj[tid];
-    ctl->assoc_new[tid] = sh.decn[tid];
-  }
-  if (dirty) {
-    double* S = A.sig[par] + f * A.sig_stride;
-    double* X = A.x[par] + f * A.x_stride;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(S, 0, n * ld * 8, 0x00020000);
-#pragma unroll
-    for (int s = 0; s < RS; ++s) {
-      const int r = row(s);
-      if (r >= n) continue;
-#pragma unroll
-      for (int t = 0; t < CS; ++t) {
-        const int c = col(t);  // columns ≥ n go out of the descriptor's range (dropped)
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, sg[s][t]), rs,
-                                              c < n ? c * 8 : kOOB, r * ld * 8, 0);
+      if ((flags & kLast) || kind == kLaunchPosterior) {  // posterior, slam.cpp:273-291 (deferred)
+        st.post = true;
+        st.podom[0] = d.odom[0];
+        st.podom[1] = d.odom[1];
+        st.podom[2] = d.odom[2];
       }
     }
-    if (rown && rl < n) X[rl] = xl;
   }
-  if (tid == 0) {
-    ctl->tmo[0] = tmo[0];
-    ctl->tmo[1] = tmo[1];
-    ctl->tmo[2] = tmo[2];
-    ctl->counter = counter;
-    if (status) atomicOr(&ctl->status, status);
-  }
+  if (st.par < 0) return;  // the plan does not name this filter
+  if (st.post) posterior_now(st, sh);
+  store_filter(st, sh, A, ctl, f);
 }
 
 hipError_t launch_resident(const PassArgs<double>& a, const PlanEntry* plan, int nplan, int flo,

@@ -6,8 +6,10 @@ Each library runs the same replays in its own child process (the headline fp32 N
 replay from an fp64 survey, fp64 N = 1024, messages of two chunks, the Joseph form, the rebuild
 without staged operands, the Joseph form in fp32 and under unknown association, four filters with
 event hand-offs, unknown association and its routes: one marker per launch, one workgroup, three
-on each transport, a map that fills, messages of two chunks); the final states are compared bit
-for bit. A pure
+on each transport, a map that fills, messages of two chunks; the resident kernel: full maps in each
+register layout, known ids and association, a map that fills, the Joseph form, a ragged 48-filter
+handle, a replay across staging blocks and flushes, the per-call surface); the final states are
+compared bit for bit. A pure
 performance change of the kernels (same formulas, same summation order) must print "identical"."""
 import os
 import subprocess
@@ -36,6 +38,19 @@ def child(tag):
             x, S, c = e.state(f)
             res[f"{name}_x{f}"], res[f"{name}_S{f}"] = x, S
             res[f"{name}_st{f}"] = np.array([e.status(f), c])
+
+    def stack(scs, T, assoc):
+        """Filter f = scenario f, ragged: replay()'s counts, rel, odom, ids (None: unknown),
+        actions."""
+        F, M = len(scs), max(s.ids.shape[1] for s in scs)
+        counts, ids = np.zeros((T, F), np.int32), np.full((T, F, M), -1, np.int32)
+        act, rel, odom = np.zeros((T, F, M), np.int32), np.zeros((T, F, M, 2)), np.zeros((T, F, 3))
+        for f, s in enumerate(scs):
+            m = s.ids.shape[1]
+            counts[:, f], ids[:, f, :m] = s.count, s.ids
+            act[:, f, :m], rel[:, f, :m] = s.actions, s.rel
+            odom[:, f] = pyekf.odometry(s)
+        return counts, rel, odom, None if assoc else ids, act
 
     # headline: fp64 survey, then fp32 N = 1024 through the device planner, and fp64 host-planned
     env()
@@ -154,6 +169,71 @@ def child(tag):
     assoc_leg("assoc_fill_2wg", 70, synth.populated(130, 6, shuffle=True), EKF_RESIDENT="0")
     # ... and messages of two chunks (24 markers) under association
     assoc_leg("assoc_multi", 96, synth.synthetic(96, 14, max_markers=24, shuffle=True))
+    # k_resident (fp64, n ≤ 128): every instantiation and branch. Full maps at N = 50 (26 row
+    # slots), 51 and 62 (32), known ids and association; N = 30 (16 row slots, one column slot)
+    # under association, where the map fills (EKF_FLAG_RANGE); the Joseph form at N = 30, 50, 62
+    def resident_leg(name, N, assoc, joseph=False):
+        env(EKF_RESIDENT="1")
+        sc = synth.populated(N, 6, shuffle=assoc)
+        odom = pyekf.odometry(sc)
+        e = pyekf.EKF(n_landmarks=N)
+        assert e.path == pyekf.EKF_PATH_RESIDENT
+        if joseph:
+            e.set_joseph(True)
+        e.replay(sc.count[:, None], sc.rel[:, None], odom[:, None],
+                 ids=None if assoc else sc.ids[:, None], actions=sc.actions[:, None], assoc=assoc)
+        keep(name, e)
+        e.close()
+
+    for N in (50, 51, 62):
+        resident_leg(f"res_full{N}_known", N, False)
+        resident_leg(f"res_full{N}_assoc", N, True)
+    resident_leg("res_fill30_assoc", 30, True)
+    for N in (30, 50, 62):  # the Joseph instantiation of each layout: 16/1, 26/2, 32/2
+        resident_leg(f"res_joseph{N}_known", N, False, joseph=True)
+        resident_leg(f"res_joseph{N}_assoc", N, True, joseph=True)
+    # ... 48 filters with different maps and ragged messages in one handle, one upload ...
+    F, T, N = 48, 24, 40
+    for assoc in (False, True):
+        scs = [synth.make_scenario(N, synth.random_landmarks(10 + f % 20, seed=300 + f), T,
+                                   max_markers=4 + f % 9, seed=400 + f, shuffle=assoc)
+               for f in range(F)]
+        e = pyekf.EKF(n_landmarks=N, n_filters=F)
+        e.replay(*stack(scs, T, assoc), assoc=assoc)
+        keep("res_ragged_" + ("assoc" if assoc else "known"), e, F)
+        e.close()
+    # ... a replay of 40 messages × 256 filters: several 16-entry staging blocks per launch, and
+    # the plan is flushed every 8192 descriptors (Σ leaves the registers and comes back) ...
+    F, T, N = 256, 40, 24
+    base = [synth.synthetic(N, T, seed=500 + k, max_markers=8) for k in range(4)]
+    e = pyekf.EKF(n_landmarks=N, n_filters=F)
+    e.replay(*stack([base[f % 4] for f in range(F)], T, False))
+    keep("res_spans_uploads", e, F)
+    e.close()
+    # ... and the per-call surface, one launch each: predict / correct / posterior on the known-id
+    # golden drive, predict / associate_correct / posterior on the association one
+    for gname in ("basic_world_known", "basic_world_assoc"):
+        g = np.load(os.path.join(ROOT, "tests", "golden", gname + ".npz"))
+        sc = synth.Scenario(int(g["n_landmarks"]), g["landmarks"], g["wheel"], g["ids"],
+                            g["actions"], g["rel"], g["count"], g["truth"], float(g["track"]),
+                            float(g["radius"]))
+        odom = pyekf.odometry(sc)
+        e = pyekf.EKF(n_landmarks=sc.n_landmarks)
+        dec = []
+        for t in range(sc.n_messages):
+            e.set_odom(odom[t])
+            e.predict()
+            for i in range(int(sc.count[t])):
+                if bool(g["assoc"]):
+                    dec.append(e.associate_correct(*sc.rel[t, i]))
+                elif sc.actions[t, i] == 0:
+                    e.correct(int(sc.ids[t, i]), *sc.rel[t, i])
+            e.posterior()
+        keep("res_percall_" + gname, e)
+        res["res_percall_dec_" + gname] = np.array(dec, dtype=np.int64)
+        res["res_percall_tmo_" + gname] = np.asarray(e.map_odom())
+        e.close()
+    env()
     # digests only (a whole fp64 Σ at N = 1024 is 34 MB): bit-identical ⇔ equal digests
     import hashlib
     import json
