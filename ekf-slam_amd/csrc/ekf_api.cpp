@@ -179,6 +179,8 @@ int ekf_destroy(ekf_t h) {
   if (h->rec) hipFree(h->rec);
   if (h->stage) hipFree(h->stage);
   if (h->ddesc) hipFree(h->ddesc);
+  if (h->trace) hipFree(h->trace);
+  if (h->trace_n) hipFree(h->trace_n);
   for (PlanState* p : h->dstate)
     if (p) hipFree(p);
   if (h->hstate) hipHostFree(h->hstate);
@@ -444,8 +446,76 @@ int ekf_reset(ekf_t h, int f) {
   HIPCHK(hipMemsetAsync(h->x[0] + f0 * h->x_stride, 0, h->x_stride * nf * sizeof(double),
                         h->stream));
   HIPCHK(hipMemsetAsync(h->ctl + f0, 0, sizeof(FilterCtl) * nf, h->stream));
+  if (h->trace)  // the filters' pose traces restart at record 0
+    HIPCHK(hipMemsetAsync(h->trace_n + f0, 0, sizeof(long long) * nf, h->stream));
   if (init_diag(h, sig0, nf)) return EKF_E_HIP;
   return drain(h);
+}
+
+// ---- the pose trace: records appended by the kernels that store a posterior t_map_odom ----
+
+int ekf_trace_enable(ekf_t h, int capacity) {
+  if (!h || capacity < 0) return EKF_E_ARG;
+  if (int rc = settle(h)) return rc;  // nothing in flight reads the buffers replaced below
+  hipSetDevice(h->cfg.device);
+  TraceRec* recs = nullptr;
+  long long* counts = nullptr;
+  if (capacity > 0) {
+    const size_t F = static_cast<size_t>(h->F);
+    // (a failed allocation must not stay behind as the runtime's last error: the launchers
+    // return hipGetLastError())
+    if (hipMalloc(&recs, F * capacity * sizeof(TraceRec)) != hipSuccess) {
+      (void)hipGetLastError();
+      return EKF_E_NOMEM;
+    }
+    if (hipMalloc(&counts, F * sizeof(long long)) != hipSuccess) {
+      (void)hipGetLastError();
+      hipFree(recs);
+      return EKF_E_NOMEM;
+    }
+    if (hipMemset(counts, 0, F * sizeof(long long)) != hipSuccess) {
+      hipFree(recs);
+      hipFree(counts);
+      return EKF_E_HIP;
+    }
+  }
+  if (h->trace) hipFree(h->trace);
+  if (h->trace_n) hipFree(h->trace_n);
+  h->trace = recs;
+  h->trace_n = counts;
+  h->trace_cap = capacity;
+  return EKF_OK;
+}
+
+int ekf_trace_count(ekf_t h, int f, long long* appended) {
+  if (!valid(h, f) || !appended || !h->trace) return EKF_E_ARG;
+  if (int rc = settle(h)) return rc;
+  HIPCHK(hipMemcpy(appended, h->trace_n + f, sizeof(long long), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_trace_read(ekf_t h, int f, long long first, int n, ekf_trace_rec* out, int* got) {
+  if (!valid(h, f) || !out || !got || !h->trace || first < 0 || n < 0) return EKF_E_ARG;
+  *got = 0;
+  if (int rc = settle(h)) return rc;
+  long long appended = 0;
+  HIPCHK(hipMemcpy(&appended, h->trace_n + f, sizeof(long long), hipMemcpyDeviceToHost));
+  const long long kept = std::min<long long>(appended, h->trace_cap);
+  if (first >= kept || n == 0) return EKF_OK;
+  const long long k = std::min<long long>(n, kept - first);
+  HIPCHK(hipMemcpy(out, h->trace + static_cast<size_t>(f) * h->trace_cap + first,
+                   static_cast<size_t>(k) * sizeof(TraceRec), hipMemcpyDeviceToHost));
+  *got = static_cast<int>(k);
+  return EKF_OK;
+}
+
+int ekf_trace_clear(ekf_t h, int f) {
+  if (!h || f >= h->F || !h->trace) return EKF_E_ARG;
+  if (int rc = settle(h)) return rc;
+  hipSetDevice(h->cfg.device);
+  const int f0 = f < 0 ? 0 : f, nf = f < 0 ? h->F : 1;
+  HIPCHK(hipMemsetAsync(h->trace_n + f0, 0, sizeof(long long) * nf, h->stream));
+  return drain(h);  // (the bulk stream's next launch is not ordered after the main stream's memset)
 }
 
 int ekf_get_pose(ekf_t h, int f, double* p) {

@@ -922,7 +922,8 @@ __device__ __forceinline__ void write_predict_factors(const AmFilter<T>& F, int 
 template <typename T>
 __device__ __forceinline__ void finish_filter(const AmFilter<T>& F, const MsgDesc& d, int flags,
                                               const double* pose, const AmChunk& ch,
-                                              unsigned* fatal) {
+                                              const PassArgs<T>& A, int f) {
+  unsigned* const fatal = A.fatal;
   if (F.g == 0 && F.lane == 0) {
     F.ctl->counter = ch.s;
     if (flags & kLast) {  // posterior t_map_odom = T(x, y, θ)·t_odom_robot⁻¹ (slam.cpp:490-494)
@@ -931,6 +932,11 @@ __device__ __forceinline__ void finish_filter(const AmFilter<T>& F, const MsgDes
       F.ctl->tmo[0] = tmo.theta;
       F.ctl->tmo[1] = tmo.x;
       F.ctl->tmo[2] = tmo.y;
+      // the pose trace's record: of a filter's ⌈N/64⌉ workgroups this one alone appends (the
+      // count's earlier writers ended before this kernel read t_map_odom, at its start)
+      if (A.trace)
+        A.trace_n[f] = trace_append(A, f, A.trace_n[f], pose[0], pose[1], pose[2], tmo.theta,
+                                    tmo.x, tmo.y);
     }
   }
   if (F.lane == 0 && F.g == 0 && ch.status) atomicOr(&F.ctl->status, ch.status);
@@ -1130,7 +1136,7 @@ __global__ __launch_bounds__(kAmThreads) void k_assoc_msg(PassArgs<T> A, AmArgs 
 
   AM_STAMP(kMaxChunk, 1);
   write_predict_factors<T, J>(F, m, first, a1, a2, sl, pose);
-  finish_filter(F, d, flags, pose, ch, A.fatal);
+  finish_filter(F, d, flags, pose, ch, A, A.f0 + fy);
   if (sizeof(T) == 4)
     write_pend_patch(sh, F, A.rec + static_cast<size_t>(d.parity) * A.rec_stride + (A.f0 + fy), m,
                      tagbase | static_cast<unsigned>(m + 1), B.spin, A.fatal, ch.any_new, sl, Pp);

@@ -122,6 +122,8 @@ struct ChainSharedT {
   double npose[3], na1, na2;  // the next chunk's predicted pose and At entries (wave 3, ahead)
   int npose_ci;               // the chunk index they belong to (−1: none)
   double tmo[3];    // t_map_odom
+  long long trace_n;  // pose trace: the filter's record count, carried over the launch's chunks
+                      // (−1: not loaded yet; wave 3's lane 0 alone reads and writes it)
   double a1, a2, s00;
   int nu_cnt;
   unsigned status;
@@ -1241,6 +1243,12 @@ __device__ __forceinline__ void chain_wave3(ChainSharedT<J>& sh, const MsgDesc& 
     sh.tmo[0] = tmo.theta;
     sh.tmo[1] = tmo.x;
     sh.tmo[2] = tmo.y;
+    if (A.trace) {  // the pose trace's record, behind the t_map_odom store (count: k_chain, step 4)
+      const long long n = trace_append(A, A.f0 + fy, sh.trace_n, sh.xU[0][0], sh.xU[0][1],
+                                       sh.xU[0][2], tmo.theta, tmo.x, tmo.y);
+      sh.trace_n = n;
+      A.trace_n[A.f0 + fy] = n;
+    }
   }
   // ... and the next chunk's predicted pose (slam.cpp:184-196), beside waves 1–2's last Z / Y
   // instead of in its prologue: its inputs are this chunk's final pose (the record's x[U] there,
@@ -1670,6 +1678,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
   // kernels (two streams without CU masks: > 32 filters with EKF_SERIAL=0), DESIGN.md §5.
   __syncthreads();
   if (tid == 0) sh.npose_ci = -1;  // (ordered before its first reader by the chunk loop's barriers)
+  if (tid == 0) sh.trace_n = -1;   // (likewise)
   bool pre = false;        // sdesc[ci & 1] was prefetched by the previous chunk's epilogue
   unsigned pending = 0;    // chain epoch of the previous chunk, not yet published (its record
                            // stores are still in flight; see the epilogue)
@@ -1743,6 +1752,10 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     ChainLoads<T, J> loads;
     issue_early_loads(loads, A.stage + static_cast<size_t>(d.parity) * A.rec_stride + f, rp, ctl,
                       tid, early);
+    // pose trace: the filter's count, once per launch, by the lane that appends (chain_wave3).
+    // Here, behind the poll of step 3, every earlier writer of this filter's t_map_odom — and so
+    // of its count — is done: where gather_block / rebuild_block load FilterCtl::tmo.
+    if (A.trace && tid == 3 * 64 && sh.trace_n < 0) sh.trace_n = A.trace_n[f];
     EKF_STAMP(14);
 
     // ---- 5. A0: the index sets ----

@@ -40,6 +40,10 @@ enum ProfSlot : int {
 }  // namespace ekfslam
 
 static_assert(EKF_RESIDENT_MAX_N == ekfslam::kResidentMaxN, "ekf.h and ekf_launch.hpp agree");
+static_assert(sizeof(ekf_trace_rec) == sizeof(ekfslam::TraceRec) &&
+                  offsetof(ekf_trace_rec, map_odom) == offsetof(ekfslam::TraceRec, map_odom) &&
+                  offsetof(ekf_trace_rec, seq) == offsetof(ekfslam::TraceRec, seq),
+              "ekf.h's trace record is the device's");
 
 struct ekf_ctx {
   ekf_config cfg{};
@@ -81,6 +85,10 @@ struct ekf_ctx {
   ekfslam::ChunkRec* rec = nullptr;
   void* stage = nullptr; // StageRec<T>[2][F]: a kLook chain's rebuild operands (kStageIn)
   ekfslam::MsgDesc* ddesc = nullptr;
+  // pose trace (ekf_trace_enable; off: all null / 0, and every launch's PassArgs says so)
+  ekfslam::TraceRec* trace = nullptr;  // [F][trace_cap]
+  long long* trace_n = nullptr;        // [F] records appended
+  int trace_cap = 0;
   size_t sig_stride = 0, x_stride = 0, km_stride = 0;
   // ekf_replay_device: the planning state lives on the device while dev_plan (ping-pong by
   // dstate_cur); the planner adopts it (adopt_device_plan) before it is used again

@@ -75,6 +75,17 @@ struct alignas(16) FilterCtl {
   int assoc_new[kMaxAssoc];
 };
 
+// One posterior of the pose trace (ekf_trace_rec of include/ekf.h, the same 64 bytes): appended by
+// whichever kernel stores the filter's t_map_odom, into trace[f][count] while count < capacity;
+// beyond that only the filter's count goes on.
+struct alignas(16) TraceRec {
+  double pose[3];      // (θ, x, y) after the message's corrections
+  double map_odom[3];  // t_map_odom as stored in FilterCtl::tmo
+  long long seq;       // the record's index in the filter's trace
+  long long reserved;  // 0
+};
+static_assert(sizeof(TraceRec) == 64, "one 64-byte line per posterior");
+
 // What the chain kernel (the sequential part of a chunk) hands to the factor kernel: with
 // r(i) = Σ_pred[i][U] and c(j) = Σ_pred[U][j], K_c[i] = r(i)·Z[:, 2c..2c+1] and
 // M_c[:, j] = Y[2c..2c+1, :]·c(j); x_i += r(i)·Zx for rows outside U, xU for rows in U.

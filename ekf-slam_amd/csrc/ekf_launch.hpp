@@ -46,7 +46,31 @@ struct PassArgs {
   int n, ld, N, f0;
   double q, r, gate;
   int joseph;           // resident path: Joseph-form Σ update (ekf_set_joseph)
+  // Pose trace (ekf_trace_enable; trace == nullptr: off, one wave-uniform test in every writer of
+  // a posterior t_map_odom). A filter's posterior writers are totally ordered — what makes
+  // FilterCtl::tmo correct — and its count is read and written under that order: plain loads and
+  // stores, no atomics.
+  TraceRec* trace;        // [F][trace_cap]
+  long long* trace_n;     // [F]: records appended so far (those beyond trace_cap are only counted)
+  int trace_cap;
 };
+
+// Appends filter f's posterior as record n of its trace and returns the filter's new count (the
+// caller stores it: where, and how often, is the writer's own business). One lane, four 16-byte
+// stores: one 64-byte line.
+template <typename T>
+__device__ __forceinline__ long long trace_append(const PassArgs<T>& A, int f, long long n,
+                                                  double p0, double p1, double p2, double t0,
+                                                  double t1, double t2) {
+  if (n < A.trace_cap) {
+    double2* r = reinterpret_cast<double2*>(A.trace + static_cast<size_t>(f) * A.trace_cap + n);
+    r[0] = double2{p0, p1};
+    r[1] = double2{p2, t0};
+    r[2] = double2{t1, t2};
+    reinterpret_cast<longlong2*>(r)[3] = longlong2{n, 0};
+  }
+  return n + 1;
+}
 
 // What every launcher below calls. With events, the launch carries them in its dispatch
 // (hipExtLaunchKernelGGL): they time the kernel's own execution, not the queueing / dispatch

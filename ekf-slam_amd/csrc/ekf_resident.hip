@@ -24,8 +24,9 @@
 // In the source, in execution order. k_resident is the plan walk; a thread's share of the filter
 // is one ResState, and every phase is a __forceinline__ function on it (one register allocation):
 //   stage_plan_block      16 plan entries' descriptors → LDS
-//   load_filter           first entry naming the filter: Σ, x, t_map_odom, counter
+//   load_filter           first entry naming the filter: Σ, x, t_map_odom, counter, trace count
 //   posterior_now / _from the deferred posterior t_map_odom (with the next gather of the pose)
+//                         and its record in the pose trace (PassArgs::trace)
 //   predict               gather_rows (pose) → barrier → Σ = AΣAᵀ + Q̄, the new pose
 //   known ids, per marker: gather_rows → barrier → correct
 //   unknown, per marker   associate_correct: gather_rows (pose), gather_assoc_blocks → barrier →
@@ -33,7 +34,7 @@
 //                         (landmark) → barrier → correct
 //   correct               innovation_gain (ẑ, H, M = HΣ, S, S⁻¹, ν, K) → apply_simple /
 //                         apply_joseph → x += Kν
-//   store_filter          decisions, Σ, x, t_map_odom, counter, status
+//   store_filter          decisions, Σ, x, t_map_odom, counter, status, trace count
 // Shared algebra: times_H (five-term products with H), gain (K = q·S⁻¹), landmark_from (a first
 // sighting's position); range_innovation and sub_rounded (ekf_math.hpp) pin the two roundings of
 // z₀ − ẑ₀.
@@ -121,6 +122,7 @@ struct ResState {
   bool post = false;
   double podom[3] = {0.0, 0.0, 0.0};
   unsigned counter = 0, status = 0;
+  long long trace_n = 0;  // pose trace: the filter's record count (workgroup-uniform)
   unsigned long long dslots = 0;  // association slots decided in this launch (sh.decj/decn)
   int par = -1;                   // current parity (−1: not loaded yet)
   bool dirty = false;             // Σ / x changed (a chunk entry ran)
@@ -224,6 +226,7 @@ __device__ __forceinline__ void load_filter(ResState<W, RS, CS>& st, const PassA
   st.tmo[1] = ctl->tmo[1];
   st.tmo[2] = ctl->tmo[2];
   st.counter = ctl->counter;
+  if (A.trace) st.trace_n = A.trace_n[f];
 }
 
 // Rows / columns idx_a with a ≥ amin (j < 0: pose only) and their x into gather buffer bb
@@ -283,36 +286,44 @@ __device__ __forceinline__ void gather_rows(ResState<W, RS, CS>& st, ResShared<W
   }
 }
 
-// posterior t_map_odom = T(x, y, θ)·t_odom_robot⁻¹ (slam.cpp:273-291) from a gathered pose
+// posterior t_map_odom = T(x, y, θ)·t_odom_robot⁻¹ (slam.cpp:273-291) from a gathered pose, and
+// the pose trace's record of it (every thread holds the pose and the count: thread 0 stores)
 template <int W, int RS, int CS>
-__device__ __forceinline__ void posterior_from(ResState<W, RS, CS>& st, double p0, double p1,
-                                               double p2) {
+__device__ __forceinline__ void posterior_from(ResState<W, RS, CS>& st, const PassArgs<double>& A,
+                                               int f, double p0, double p1, double p2) {
   const Pose2 t = compose_sc(Pose2{p0, p1, p2},
                              inverse_sc(Pose2{st.podom[0], st.podom[1], st.podom[2]}));
   st.tmo[0] = t.theta;
   st.tmo[1] = t.x;
   st.tmo[2] = t.y;
   st.post = false;
+  if (A.trace) {
+    if (threadIdx.x == 0) trace_append(A, f, st.trace_n, p0, p1, p2, t.theta, t.x, t.y);
+    st.trace_n += 1;
+  }
 }
 template <int W, int RS, int CS>
-__device__ __forceinline__ void posterior_now(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh) {
+__device__ __forceinline__ void posterior_now(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                              const PassArgs<double>& A, int f) {
   st.b ^= 1;
   if (st.rown && st.rl < 3) sh.gx[st.b][st.rl] = st.xl;
   __syncthreads();
-  posterior_from(st, sh.gx[st.b][0], sh.gx[st.b][1], sh.gx[st.b][2]);
+  posterior_from(st, A, f, sh.gx[st.b][0], sh.gx[st.b][1], sh.gx[st.b][2]);
 }
 
 // predict, slam.cpp:184-198: Σ = AΣAᵀ + Q̄, A = I + α·e0ᵀ; the last message's deferred posterior
 // rides on its pose gather
 template <int W, int RS, int CS>
-__device__ __forceinline__ void predict(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh, int n,
-                                        double q, const double* odom) {
+__device__ __forceinline__ void predict(ResState<W, RS, CS>& st, ResShared<W, RS, CS>& sh,
+                                        const PassArgs<double>& A, int f, const double* odom) {
+  const int n = A.n;
+  const double q = A.q;
   st.b ^= 1;
   const int b = st.b;
   gather_rows(st, sh, n, b, -8, 0);
   __syncthreads();
   const double prev[3] = {sh.gx[b][0], sh.gx[b][1], sh.gx[b][2]};
-  if (st.post) posterior_from(st, prev[0], prev[1], prev[2]);
+  if (st.post) posterior_from(st, A, f, prev[0], prev[1], prev[2]);
   const Pose2 cur = compose_sc(Pose2{st.tmo[0], st.tmo[1], st.tmo[2]},
                                Pose2{odom[0], odom[1], odom[2]});
   const double a1 = -(cur.y - prev[2]), a2 = cur.x - prev[1];
@@ -645,6 +656,7 @@ __device__ __forceinline__ void store_filter(ResState<W, RS, CS>& st, ResShared<
     ctl->tmo[1] = st.tmo[1];
     ctl->tmo[2] = st.tmo[2];
     ctl->counter = st.counter;
+    if (A.trace) A.trace_n[f] = st.trace_n;
     if (st.status) atomicOr(&ctl->status, st.status);
   }
 }
@@ -678,9 +690,9 @@ __global__ __launch_bounds__(W * 64) void k_resident(PassArgs<double> A, const P
       if (!(flags & kActive)) continue;
       if (st.par < 0) load_filter(st, A, ctl, f, d.parity);  // first entry naming this filter
       if (st.post && kind != kLaunchPosterior && !(flags & kFirst))
-        posterior_now(st, sh);  // corrections follow
+        posterior_now(st, sh, A, f);  // corrections follow
       if (kind != kLaunchPosterior) {
-        if (flags & kFirst) predict(st, sh, A.n, A.q, d.odom);
+        if (flags & kFirst) predict(st, sh, A, f, d.odom);
         if (kind == kLaunchKnown) {  // known association, slam.cpp:201-271
           for (int c = 0; c < d.m; ++c) {
             const int id = d.ids[c];
@@ -700,6 +712,9 @@ __global__ __launch_bounds__(W * 64) void k_resident(PassArgs<double> A, const P
         st.dirty = true;
       }
       if ((flags & kLast) || kind == kLaunchPosterior) {  // posterior, slam.cpp:273-291 (deferred)
+        // a posterior still owed here (only an ekf_posterior entry leaves one) would be overwritten
+        // by this one: the same t_map_odom, but the pose trace owes it a record of its own
+        if (st.post && A.trace) posterior_now(st, sh, A, f);
         st.post = true;
         st.podom[0] = d.odom[0];
         st.podom[1] = d.odom[1];
@@ -708,7 +723,7 @@ __global__ __launch_bounds__(W * 64) void k_resident(PassArgs<double> A, const P
     }
   }
   if (st.par < 0) return;  // the plan does not name this filter
-  if (st.post) posterior_now(st, sh);
+  if (st.post) posterior_now(st, sh, A, f);
   store_filter(st, sh, A, ctl, f);
 }
 

@@ -41,6 +41,9 @@ PassArgs<T> args(ekf_ctx* h, const MsgDesc* desc, int f0) {
   a.r = h->cfg.r_noise;
   a.gate = h->cfg.mah_gate;
   a.joseph = h->plan.joseph() ? 1 : 0;
+  a.trace = h->trace;
+  a.trace_n = h->trace_n;
+  a.trace_cap = h->trace_cap;
   return a;
 }
 

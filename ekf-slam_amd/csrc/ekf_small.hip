@@ -21,6 +21,8 @@ __global__ void k_posterior(PassArgs<T> A, int nf) {
   ctl->tmo[0] = tmo.theta;
   ctl->tmo[1] = tmo.x;
   ctl->tmo[2] = tmo.y;
+  if (A.trace)  // the pose trace's record (one thread per filter)
+    A.trace_n[f] = trace_append(A, f, A.trace_n[f], x[0], x[1], x[2], tmo.theta, tmo.x, tmo.y);
 }
 
 template <typename T>

@@ -2,6 +2,7 @@
 #include "slam_core.h"
 
 #include <new>
+#include <vector>
 
 #include "geom.hpp"
 
@@ -14,6 +15,7 @@ struct slam_core {
   Pose2 t_odom_robot{};          // slam.cpp:650
   double track = 0.160, radius = 0.033;
   int source = SLAM_SOURCE_SIM;
+  int trace_cap = 0;             // the pose trace's capacity as slam_replay_trace last set it
 };
 
 extern "C" {
@@ -109,6 +111,63 @@ int slam_replay(slam_t s, int T, int ticks, const double* wheel, int m_max, cons
   if (defer) {
     const int rc = ekf_defer(s->ekf, 0);
     if (rc && !first_rc) first_rc = rc;
+  }
+  return first_rc;
+}
+
+int slam_replay_trace(slam_t s, int T, int ticks, const double* wheel, int m_max,
+                      const int* counts, const int* ids, const int* actions, const double* rel_xy,
+                      double* out_pose, double* out_tmo) {
+  if (!s || T < 0 || ticks < 0 || !wheel || !counts || (m_max > 0 && !rel_xy)) return EKF_E_ARG;
+  // row −1: what slam_replay would read before the drive
+  double pose[3], tmo[3];
+  if (int rc = ekf_get_pose(s->ekf, 0, pose)) return rc;
+  if (int rc = ekf_get_map_odom(s->ekf, 0, tmo)) return rc;
+  // the filter's trace, wide enough for the drive and empty (cleared; enabled again if somebody
+  // turned it off through slam_filter)
+  if (T > s->trace_cap || ekf_trace_clear(s->ekf, 0) != EKF_OK) {
+    const int cap = T > s->trace_cap ? T : s->trace_cap;
+    if (int rc = ekf_trace_enable(s->ekf, cap > 0 ? cap : 1)) return rc;
+    s->trace_cap = cap > 0 ? cap : 1;
+  }
+  int first_rc = EKF_OK;
+  std::vector<char> has(static_cast<size_t>(T), 0);  // message t appended a record
+  int n_rec = 0;
+  ekf_defer(s->ekf, 1);
+  for (int t = 0; t < T; ++t) {
+    for (int k = 0; k < ticks; ++k) {
+      const double* w = wheel + (static_cast<size_t>(t) * ticks + k) * 2;
+      slam_joint_states(s, w[0], w[1]);
+    }
+    const size_t o = static_cast<size_t>(t) * m_max;
+    const int rc = slam_markers(s, counts[t], ids ? ids + o : nullptr,
+                                actions ? actions + o : nullptr, rel_xy + 2 * o);
+    if (rc && !first_rc) first_rc = rc;
+    has[t] = rc == EKF_OK;
+    n_rec += rc == EKF_OK;
+  }
+  {
+    const int rc = ekf_defer(s->ekf, 0);
+    if (rc && !first_rc) first_rc = rc;
+  }
+  std::vector<ekf_trace_rec> recs(static_cast<size_t>(n_rec > 0 ? n_rec : 1));
+  int got = 0;
+  if (int rc = ekf_trace_read(s->ekf, 0, 0, n_rec, recs.data(), &got)) return rc;
+  if (got != n_rec) return first_rc ? first_rc : EKF_E_ARG;  // (the trace was resized meanwhile)
+  int r = 0;
+  for (int t = 0; t < T; ++t) {
+    if (has[t]) {
+      for (int k = 0; k < 3; ++k) {
+        pose[k] = recs[r].pose[k];
+        tmo[k] = recs[r].map_odom[k];
+      }
+      ++r;
+    }
+    // (a message without a record repeats the row before it: slam_replay reads an unchanged pose)
+    for (int k = 0; k < 3; ++k) {
+      if (out_pose) out_pose[3 * static_cast<size_t>(t) + k] = pose[k];
+      if (out_tmo) out_tmo[3 * static_cast<size_t>(t) + k] = tmo[k];
+    }
   }
   return first_rc;
 }

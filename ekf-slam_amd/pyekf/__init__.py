@@ -38,6 +38,7 @@ EXPORTS = [
     "ekf_get_map_odom", "ekf_get_state", "ekf_set_state", "ekf_get_status", "ekf_defer",
     "ekf_set_joseph",
     "ekf_reset", "slam_reset",
+    "ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear", "slam_replay_trace",
     "ekf_profile_enable", "ekf_profile_read", "ekf_sigma_pass_bytes", "ekf_normalize_angle",
     "ekf_debug_poison_lds",
     "slam_create", "slam_destroy", "slam_joint_states", "slam_markers", "slam_initial_pose",
@@ -49,6 +50,8 @@ EXPORTS = [
     "ekf_sim_config_default", "ekf_sim_create", "ekf_sim_destroy", "ekf_sim_run",
     "ekf_sim_markers", "ekf_sim_poses",
 ]
+TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear",
+                 "slam_replay_trace")
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
 
 
@@ -72,6 +75,17 @@ class ScanConfig(C.Structure):
     _fields_ = [("seed", C.c_ulonglong), ("scan0", C.c_longlong),
                 ("arena_w", C.c_double), ("arena_h", C.c_double),
                 ("range_min", C.c_double), ("range_max", C.c_double), ("sigma", C.c_double)]
+
+
+class TraceRec(C.Structure):
+    """ekf_trace_rec (include/ekf.h): one posterior of a filter's pose trace, 64 bytes."""
+    _fields_ = [("pose", C.c_double * 3), ("map_odom", C.c_double * 3),
+                ("seq", C.c_longlong), ("reserved", C.c_longlong)]
+
+
+TRACE_DTYPE = np.dtype([("pose", np.float64, 3), ("map_odom", np.float64, 3),
+                        ("seq", np.int64), ("reserved", np.int64)])
+assert TRACE_DTYPE.itemsize == C.sizeof(TraceRec) == 64
 
 
 class Config(C.Structure):
@@ -123,6 +137,11 @@ def lib():
             "ekf_set_joseph": (_i, [_vp, _i]),
             "ekf_reset": (_i, [_vp, _i]),
             "slam_reset": (_i, [_vp]),
+            "ekf_trace_enable": (_i, [_vp, _i]),
+            "ekf_trace_count": (_i, [_vp, _i, C.POINTER(C.c_longlong)]),
+            "ekf_trace_read": (_i, [_vp, _i, C.c_longlong, _i, _vp, _ip]),
+            "ekf_trace_clear": (_i, [_vp, _i]),
+            "slam_replay_trace": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
             "ekf_profile_enable": (_i, [_vp, _i]),
             "ekf_profile_read": (_i, [_vp, _i, C.POINTER(C.c_longlong), _dp]),
             "ekf_sigma_pass_bytes": (C.c_double, [_vp, _i]),
@@ -159,6 +178,10 @@ def lib():
             "ekf_sim_poses": (_i, [_vp, _vp, _vp]),
         }
         for name, (res, argt) in sig.items():
+            # (EKF_LIB naming a library built from an earlier commit, for the A/B tools: it loads
+            # without the pose trace, and a call of it fails; build() checks EXPORTS)
+            if name in TRACE_EXPORTS and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = argt
@@ -371,6 +394,32 @@ class EKF:
     def set_joseph(self, on=True) -> int:
         return lib().ekf_set_joseph(self.h, int(on))
 
+    # the pose trace (ekf_trace_*): every message's posterior, recorded on the device
+    def trace_enable(self, capacity):
+        """Keep up to `capacity` records per filter (0: off and freed). Reallocates and clears."""
+        _check(lib().ekf_trace_enable(self.h, int(capacity)), "ekf_trace_enable")
+
+    def trace_count(self, f=0) -> int:
+        """Records appended to filter f's trace (those beyond the capacity are only counted)."""
+        n = C.c_longlong(0)
+        _check(lib().ekf_trace_count(self.h, f, C.byref(n)), "ekf_trace_count")
+        return n.value
+
+    def trace(self, f=0, first=0, n=None):
+        """Records [first, first + n) of filter f's trace that are kept (n = None: all from
+        `first` on): (pose [k, 3], map_odom [k, 3], seq [k]). Synchronises."""
+        if n is None:
+            n = max(self.trace_count(f) - first, 0)
+        buf = np.zeros(max(n, 1), TRACE_DTYPE)
+        got = C.c_int(0)
+        _check(lib().ekf_trace_read(self.h, f, first, n, _ptr(buf), C.byref(got)),
+               "ekf_trace_read")
+        buf = buf[:got.value]
+        return buf["pose"].copy(), buf["map_odom"].copy(), buf["seq"].copy()
+
+    def trace_clear(self, f=-1):
+        _check(lib().ekf_trace_clear(self.h, f), "ekf_trace_clear")
+
     def status(self, f=0) -> int:
         fl = C.c_uint(0)
         _check(lib().ekf_get_status(self.h, f, C.byref(fl)), "ekf_get_status")
@@ -457,16 +506,19 @@ class Slam:
         _check(lib().ekf_get_state(ekf, 0, _ptr(x), _ptr(S), C.byref(cnt)), "ekf_get_state")
         return x, S, cnt.value
 
-    def replay(self, sc, poses=True):
-        """Drive a synth.Scenario (wheel ticks + marker arrays) natively through the node mirror."""
+    def replay(self, sc, poses=True, trace=False):
+        """Drive a synth.Scenario (wheel ticks + marker arrays) natively through the node mirror.
+        trace: slam_replay_trace — the drive runs deferred and the per-message outputs come from
+        the filter's pose trace."""
         T, ticks = sc.wheel.shape[0], sc.wheel.shape[1]
         M = sc.ids.shape[1]
         wheel, counts = _f64(sc.wheel), _i32(sc.count)
         ids, act, rel = _i32(sc.ids), _i32(sc.actions), _f64(sc.rel)
         out_p = np.zeros((T, 3)) if poses else None
         out_t = np.zeros((T, 3)) if poses else None
-        rc = lib().slam_replay(self.h, T, ticks, _ptr(wheel), M, _ptr(counts), _ptr(ids),
-                               _ptr(act), _ptr(rel), _ptr(out_p), _ptr(out_t))
+        fn = lib().slam_replay_trace if trace else lib().slam_replay
+        rc = fn(self.h, T, ticks, _ptr(wheel), M, _ptr(counts), _ptr(ids), _ptr(act), _ptr(rel),
+                _ptr(out_p), _ptr(out_t))
         return rc, out_p, out_t
 
 

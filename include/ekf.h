@@ -151,7 +151,8 @@ int ekf_batch_sensor(ekf_t h, int assoc, int m_max, const int* counts, const int
 
 /* Replay T messages through ekf_batch_sensor (arrays as there, with a leading [T] axis):
  * counts[T][F], ids/actions[T][F][m_max], rel_xy[T][F][m_max][2], odom[T][F][3].
- * out_pose[T][F][3] (nullable) receives each posterior pose and makes every message synchronous. */
+ * out_pose[T][F][3] (nullable) receives each posterior pose and makes every message synchronous;
+ * the pose trace below (ekf_trace_enable) records the same poses without that. */
 int ekf_replay(ekf_t h, int assoc, int T, int m_max, const int* counts, const int* ids,
                const int* actions, const double* rel_xy, const double* odom, double* out_pose);
 
@@ -226,7 +227,8 @@ int ekf_set_joseph(ekf_t h, int on);
  * goes to the device in one upload (and, on the resident path, one kernel launch) when it reaches
  * 8192 descriptors, when a synchronising call below needs the state, or when deferral is turned
  * off (which submits what is planned). Off by default: each callback is submitted as it is made.
- * A replay driver with no per-message outputs (slam_replay) turns it on. */
+ * A replay driver with no per-message outputs (slam_replay) turns it on, and so does one that takes
+ * them from the pose trace (slam_replay_trace). */
 int ekf_defer(ekf_t h, int on);
 
 /* Back to the constructor's state (slam.cpp:127-139) on the device for filter `filter`, or every
@@ -254,6 +256,43 @@ int ekf_get_state(ekf_t h, int filter, double* state, double* sigma, unsigned* c
 int ekf_set_state(ekf_t h, int filter, const double* state, const double* sigma,
                   const double* t_map_odom, unsigned counter);
 int ekf_get_status(ekf_t h, int filter, unsigned* flags); /* and clears them */
+
+/* ---- the pose trace: every message's posterior, recorded on the device ---- */
+/* The per-message outputs of the reference node (the posterior pose and t_map_odom it publishes as
+ * TF, green/odom and green/path after every MarkerArray, slam.cpp:273-291) without a
+ * synchronisation per message: the kernels append them to a per-filter buffer in device memory,
+ * read back whenever the caller likes.
+ *   Off by default. A handle that never enables the trace behaves exactly as without it, bit for
+ *     bit, with the same launches.
+ *   One record per posterior: a filter gets a record wherever a kernel stores its t_map_odom, i.e.
+ *     once per message, in whichever form it arrived (ekf_fake_sensor, ekf_sensor,
+ *     ekf_batch_sensor, ekf_replay, ekf_replay_device, ekf_replay_device_assoc, lm_replay_into,
+ *     ekf_sim_run; deferred or not), and once per ekf_posterior. A message a filter sits out
+ *     (count <= 0) appends nothing; a message whose markers are all DELETE (predict + posterior)
+ *     appends one; a message split over several chunks appends one, from its last chunk.
+ *   Beyond `capacity`, records are counted, not written (as lm_detect counts the markers beyond
+ *     max_markers): ekf_trace_count returns how many were appended, ekf_trace_read copies
+ *     [first, first + n) ∩ [0, min(appended, capacity)) and sets *got to how many that is.
+ *   ekf_trace_enable, _count, _read and _clear synchronise like ekf_get_* (they submit what is
+ *     planned and wait for both streams).
+ *   ekf_trace_enable on a handle that already traces reallocates and clears; capacity 0 turns the
+ *     trace off and frees it. ekf_reset(h, f) restarts filter f's trace at record 0 (every
+ *     filter's for f < 0); ekf_set_state leaves it alone. With the trace on, the filter's state,
+ *     Σ, decisions and status are bit-identical to the trace being off.
+ *   EKF_E_ARG: a NULL handle or output, capacity < 0, filter out of range, ekf_trace_count / _read /
+ *     _clear on a handle whose trace is off, first < 0, n < 0. EKF_E_NOMEM: the
+ *     n_filters·capacity·64 bytes cannot be allocated; nothing changes then. */
+typedef struct {      /* 64 bytes, one per posterior */
+  double pose[3];     /* state(0..2) = (θ, x, y) after the message's corrections */
+  double map_odom[3]; /* t_map_odom = T(x, y, θ)·t_odom_robot⁻¹ as stored for the filter */
+  long long seq;      /* index of this record in the filter's trace (0, 1, …) */
+  long long reserved; /* 0 */
+} ekf_trace_rec;
+
+int ekf_trace_enable(ekf_t h, int capacity); /* records kept per filter; 0 = off and freed */
+int ekf_trace_count(ekf_t h, int filter, long long* appended);
+int ekf_trace_read(ekf_t h, int filter, long long first, int n, ekf_trace_rec* out, int* got);
+int ekf_trace_clear(ekf_t h, int filter); /* filter < 0: every filter */
 
 /* ---- helpers ---- */
 /* turtlelib::normalize_angle (geometry2d.cpp:5-14): maps into (-π, π], -π → π. */

@@ -45,6 +45,17 @@ ekf_t slam_filter(slam_t s);
 int slam_replay(slam_t s, int T, int ticks, const double* wheel, int m_max, const int* counts,
                 const int* ids, const int* actions, const double* rel_xy, double* out_pose,
                 double* out_tmo);
+/* slam_replay with both per-message outputs and none of their cost: the drive runs deferred, as
+ * slam_replay does when no output is asked for (on the resident path one kernel launch for the
+ * whole drive), and out_pose / out_tmo [T][3] (nullable) are filled afterwards from the filter's
+ * pose trace (ekf_trace_*, ekf.h), which the call enables with capacity >= T and clears first; it
+ * stays enabled. Message t has a record when slam_markers returned EKF_OK for it; a message without
+ * one (an empty MarkerArray, rejected ids) repeats the row before it, as slam_replay reads an
+ * unchanged pose there, and row -1 is the pose and t_map_odom read before the drive. Synchronises.
+ * Returns the first non-OK status like slam_replay. */
+int slam_replay_trace(slam_t s, int T, int ticks, const double* wheel, int m_max,
+                      const int* counts, const int* ids, const int* actions, const double* rel_xy,
+                      double* out_pose, double* out_tmo);
 /* t_odom_robot after each message's `ticks` joint_states, from a fresh DiffDrive (replay input
  * preparation): wheel[T][ticks][2] → out_odom[T][3]. */
 int slam_integrate_odometry(double track_width, double wheel_radius, int T, int ticks,
