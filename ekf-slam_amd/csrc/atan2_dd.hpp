@@ -1,5 +1,6 @@
 // atan2 in double-double arithmetic, rounded once: the bearing of a marker for the device planner
-// of association replays (plan_assoc.hpp). The host planner takes its bearings from glibc's atan2,
+// of association replays (plan_assoc.hpp) and for the resident path's replays from device memory
+// (stage_replay_block, ekf_resident.hip). The host planner takes its bearings from glibc's atan2,
 // which is correctly rounded for all but about one argument in a thousand; ocml's on the device
 // differs from it in the last bit far more often, and the landmark prior's
 // 1e7 − (1e7 − δ) (slam.cpp:130) amplifies each such bit to ≈ 1e-9 on the state. Rounding an

@@ -327,6 +327,17 @@ int ekf_replay_device_assoc(ekf_t h, int T, int m_max, const int* d_counts, cons
                              nullptr);
 }
 
+int ekf_replay_resident(ekf_t h, int assoc, int T, int m_max, const int* d_counts,
+                        const int* d_ids, const int* d_actions, const double* d_xy, int xy_stride,
+                        const double* d_odom) {
+  if (!h || T < 1 || m_max < 1 || m_max > kMaxAssoc || xy_stride < 2 || !d_counts || !d_xy ||
+      !d_odom || (!assoc && !d_ids))
+    return EKF_E_ARG;
+  if (!h->resident) return EKF_E_ARG;
+  return replay_resident(h, assoc, T, m_max, d_counts, d_ids, d_actions, d_xy, xy_stride, d_odom,
+                         nullptr, nullptr, nullptr);
+}
+
 int ekf_get_decisions(ekf_t h, int f, int m, int* assoc_out, int* is_new_out) {
   if (!valid(h, f) || m < 0 || m > kMaxAssoc) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;

@@ -173,4 +173,11 @@ int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const
                         int xy_stride, const double* d_odom, const double* host_odom,
                         hipEvent_t ready, hipEvent_t planned);
 
+// Resident handles: T messages from device memory in one launch of k_resident_replay. assoc = 0:
+// known ids (d_ids, nullable d_actions), 1: unknown association. host_odom / ready as above;
+// consumed (nullable): recorded behind the kernel, which reads its inputs for the whole launch.
+int replay_resident(ekf_ctx* h, int assoc, int T, int m_max, const int* d_counts, const int* d_ids,
+                    const int* d_actions, const double* d_xy, int xy_stride, const double* d_odom,
+                    const double* host_odom, hipEvent_t ready, hipEvent_t consumed);
+
 }  // namespace ekfslam

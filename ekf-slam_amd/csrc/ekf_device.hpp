@@ -174,8 +174,8 @@ struct alignas(16) PlanEntry {
 };
 
 // A filter's planning state between messages: the host planner's mirror (ekf_plan.hpp), and what a
-// known-association replay planned on the GPU (plan_kernels.hip, ekf_replay_device) reads before
-// and leaves after a replay.
+// device replay (the planners of plan_kernels.hip; k_resident_replay, ekf_resident.hip) reads
+// before and leaves after a replay.
 struct alignas(16) PlanState {
   int parity;    // Σ / x copy that is "in"
   int prev_m;    // markers of the filter's last pipelined chunk (−1: none, the next one gathers)

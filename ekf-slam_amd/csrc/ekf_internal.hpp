@@ -39,4 +39,11 @@ int replay_markers(ekf_t h, int device, int T, int m_max, const int* d_counts,
                    const double* d_markers, const double* odom, hipEvent_t ready,
                    hipEvent_t planned);
 
+// The same for a resident handle (lm_replay_resident): one launch of k_resident_replay reads the
+// markers in place for the whole replay, so `consumed` is recorded behind that kernel. EKF_E_ARG
+// as ekf_replay_resident's, and for a handle on another device.
+int replay_markers_resident(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                            const double* d_markers, const double* odom, hipEvent_t ready,
+                            hipEvent_t consumed);
+
 }  // namespace ekfslam

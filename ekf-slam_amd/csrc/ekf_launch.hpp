@@ -151,6 +151,25 @@ hipError_t launch_resident(const PassArgs<double>& a, const PlanEntry* plan, int
                            int nfil, hipStream_t s, hipEvent_t e0 = nullptr,
                            hipEvent_t e1 = nullptr);
 
+// Resident path, a replay whose inputs lie in device memory (k_resident_replay, ekf_replay_resident):
+// one workgroup per filter walks the T messages itself, no descriptors. The layouts of the two
+// device-planned replays below; PlanState (ekf_device.hpp) before and after.
+struct ResidentReplayArgs {
+  const int* counts;      // [T][F]; ≤ 0: no message, > M: clamped to M
+  const int* ids;         // known ids: [T][F][M]
+  const int* actions;     // known ids: [T][F][M] or null
+  const double* xy;       // marker i of (t, f): xy[((t·F + f)·M + i)·stride + {0, 1}]
+  const double* odom;     // [T][F][3]
+  const PlanState* st_in; // [F]
+  PlanState* st_out;      // [F]
+  int T, F, M;            // M ≤ kMaxAssoc
+  int stride;             // doubles between markers (2: packed pairs, 4: lm_marker)
+  int assoc;              // 0: known ids, 1: unknown association
+};
+hipError_t launch_resident_replay(const PassArgs<double>& a, const ResidentReplayArgs& r,
+                                  hipStream_t s, hipEvent_t e0 = nullptr,
+                                  hipEvent_t e1 = nullptr);
+
 // Known-association replay planned on the GPU (plan_kernels.hip, ekf_replay_device): PlanState
 // (ekf_device.hpp) before and after a replay.
 struct ReplayArgs {

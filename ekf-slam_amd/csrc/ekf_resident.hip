@@ -35,6 +35,9 @@
 //   correct               innovation_gain (ẑ, H, M = HΣ, S, S⁻¹, ν, K) → apply_simple /
 //                         apply_joseph → x += Kν
 //   store_filter          decisions, Σ, x, t_map_odom, counter, status, trace count
+// k_resident_replay (below k_resident) is the same walk over messages whose inputs lie in device
+// memory (ekf_replay_resident): stage_replay_block turns 8 messages' counts, markers and odometry
+// into (range, bearing) lists in LDS, and the phases above run on them with no descriptors.
 // Shared algebra: times_H (five-term products with H), gain (K = q·S⁻¹), landmark_from (a first
 // sighting's position); range_innovation and sub_rounded (ekf_math.hpp) pin the two roundings of
 // z₀ − ẑ₀.
@@ -42,7 +45,10 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <type_traits>
 
+#include "atan2_dd.hpp"
+#include "ekf.h"
 #include "ekf_device.hpp"
 #include "ekf_launch.hpp"
 #include "ekf_math.hpp"
@@ -747,6 +753,234 @@ hipError_t launch_resident(const PassArgs<double>& a, const PlanEntry* plan, int
     a.joseph ? go(k_resident<4, 26, 2, true>, 4) : go(k_resident<4, 26, 2, false>, 4);
   else
     a.joseph ? go(k_resident<4, 32, 2, true>, 4) : go(k_resident<4, 32, 2, false>, 4);
+  return hipGetLastError();
+}
+
+// ---- device-input replays (ekf_replay_resident): the same phases, fed from device memory ----
+
+namespace {
+
+constexpr int kRBlk = 8;  // messages staged per block: two per wave
+
+// A block of one filter's messages as the walk reads them.
+struct ReplayShared {
+  int m[kRBlk];  // corrections of the message (known ids: its non-DELETE markers); −1: no message
+  double odom[kRBlk][3];
+  int ids[kRBlk][kMaxAssoc];
+  double z[kRBlk][kMaxAssoc][2];  // (range, bearing), slam.cpp:208-210 / :346-347
+};
+
+// x·x + y·y rounds product by product, as the host planner's std::pow(x, 2) + std::pow(y, 2)
+__device__ __forceinline__ double marker_range(double x, double y) {
+#pragma clang fp contract(off)
+  return sqrt(x * x + y * y);
+}
+
+// The replay's arguments, read where they lie in the kernel's argument segment each time a block
+// is staged (and once more for the state hand-over) instead of being held in SGPRs for the whole
+// walk: the walk has none to spare, and an SGPR it spills costs the Joseph instantiations a VGPR.
+// ReplayKernArgs mirrors k_resident_replay's parameter list (A, R): the argument segment lays
+// parameters out like members, each at its own alignment, so R lies at offsetof(…, R) as long as
+// the kernel takes exactly these two, in this order (the asserts hold the alignments to that).
+struct ReplayKernArgs {
+  PassArgs<double> A;
+  ResidentReplayArgs R;
+};
+static_assert(alignof(ResidentReplayArgs) <= 8 && alignof(PassArgs<double>) <= 8 &&
+                  sizeof(PassArgs<double>) % alignof(ResidentReplayArgs) == 0 &&
+                  offsetof(ReplayKernArgs, R) == sizeof(PassArgs<double>),
+              "R follows A in the kernel-argument segment without padding");
+typedef const ResidentReplayArgs __attribute__((address_space(4))) * ReplayArgsPtr;
+__device__ __forceinline__ ReplayArgsPtr replay_args() {
+  typedef const char __attribute__((address_space(4))) * Bytes;
+  return reinterpret_cast<ReplayArgsPtr>(
+      (Bytes)__builtin_amdgcn_kernarg_segment_ptr() +
+      offsetof(ReplayKernArgs, R));
+}
+
+// (field by field: the struct's copy constructor takes a generic reference)
+__device__ __forceinline__ ResidentReplayArgs fetch_replay_args(ReplayArgsPtr p) {
+  asm volatile("" : "+s"(p));  // opaque: the loads stay here, nothing is hoisted out of the walk
+  ResidentReplayArgs r;
+  r.counts = p->counts;
+  r.ids = p->ids;
+  r.actions = p->actions;
+  r.xy = p->xy;
+  r.odom = p->odom;
+  r.st_in = p->st_in;
+  r.st_out = p->st_out;
+  r.T = p->T;
+  r.F = p->F;
+  r.M = p->M;
+  r.stride = p->stride;
+  r.assoc = p->assoc;
+  return r;
+}
+
+// Stage messages [t0, t0 + kRBlk) ∩ [0, T) of filter f: wave w takes messages w and w + W, lane i
+// marker i of each (m_max ≤ 64), so every load of the block is in flight at once and every
+// (range, bearing) is formed in parallel, behind one barrier pair. Known ids: the non-DELETE
+// markers of the first min(count, m_max) are compacted in order by ballot (slam.cpp:205's skip).
+// Returns the number of messages staged.
+template <int W, bool ASSOC>
+__device__ __forceinline__ int stage_replay_block(ReplayShared& rs, ReplayArgsPtr Rp, int t0,
+                                                  int f) {
+  const ResidentReplayArgs R = fetch_replay_args(Rp);
+  const int nb = min(kRBlk, R.T - t0);
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
+  __syncthreads();  // the previous block's messages are consumed
+  constexpr int kPer = kRBlk / W;
+  int cnt[kPer], id[kPer];
+  double x[kPer], y[kPer], od[kPer];
+  bool del[kPer];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {  // the loads of both messages first
+    const int e = w + W * k;
+    cnt[k] = 0;
+    id[k] = -1;
+    del[k] = false;
+    x[k] = y[k] = od[k] = 0.0;
+    if (e < nb) {
+      const size_t tf = static_cast<size_t>(t0 + e) * R.F + f;
+      cnt[k] = min(R.counts[tf], R.M);
+      if (lane < 3) od[k] = R.odom[tf * 3 + lane];
+      if (lane < cnt[k]) {
+        const size_t o = tf * R.M + lane;
+        x[k] = R.xy[o * R.stride];
+        y[k] = R.xy[o * R.stride + 1];
+        if constexpr (!ASSOC) {
+          id[k] = R.ids[o];
+          del[k] = R.actions && R.actions[o] == EKF_MARKER_DELETE;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const int e = w + W * k;
+    if (e >= nb) continue;
+    const bool add = lane < cnt[k] && !del[k];
+    const unsigned long long bal = __ballot(add);
+    const int pos = static_cast<int>(__popcll(bal & ((1ull << lane) - 1ull)));
+    if (add) {
+      rs.ids[e][pos] = id[k];
+      rs.z[e][pos][0] = marker_range(x[k], y[k]);
+      rs.z[e][pos][1] = atan2_rounded(y[k], x[k]);
+    }
+    if (lane == 0) rs.m[e] = cnt[k] > 0 ? static_cast<int>(__popcll(bal)) : -1;
+    if (lane < 3) rs.odom[e][lane] = od[k];
+    // one message's bearings at a time: interleaved, the two double-double atan2 take more
+    // registers than the Joseph instantiations have left beside Σ
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __syncthreads();
+  return nb;
+}
+
+}  // namespace
+
+// One workgroup per filter blockIdx.x walks the replay's T messages in order: per message with
+// count > 0 the predict, its corrections (known ids: first sightings initialise, an id outside
+// [0, N) is skipped and flagged; unknown: associate_correct, slot = the marker's index) and the
+// posterior, deferred to the next gather of the pose as in k_resident. Σ and x are loaded at the
+// filter's first message from the copy st_in[f].parity names and stored back once, to that same
+// copy: every element is in a register of the thread that stores it, nothing else reads the
+// filter during the launch, so the parity does not move. A filter with no message is neither
+// loaded nor stored. Every workgroup leaves its filter's PlanState for the host planner.
+// The parameter list must stay (A, R), nothing before or between them: R is left unnamed and read
+// through replay_args() at its offset in the argument segment (ReplayKernArgs above).
+template <int W, int RS, int CS, bool JOSEPH, bool ASSOC>
+__global__ __launch_bounds__(W * 64) void k_resident_replay(PassArgs<double> A,
+                                                            ResidentReplayArgs) {
+  static_assert(RS <= 32 && kRBlk % W == 0, "as k_resident; whole messages per wave");
+  ReplayArgsPtr Rp = replay_args();
+  const int T = Rp->T;
+  __shared__ ResShared<W, RS, CS> sh;
+  __shared__ ReplayShared rs;
+  const int f = blockIdx.x;
+  FilterCtl* ctl = A.ctl + f;
+  ResState<W, RS, CS> st;
+  st.lane = threadIdx.x & 63;
+  st.w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  st.wq = st.w;
+  st.rown = st.lane < RS;
+  st.rl = st.w + W * (st.rown ? st.lane : RS - 1);
+
+  for (int t0 = 0; t0 < T; t0 += kRBlk) {
+    const int nb = stage_replay_block<W, ASSOC>(rs, Rp, t0, f);
+    for (int e = 0; e < nb; ++e) {
+      const int m = __builtin_amdgcn_readfirstlane(rs.m[e]);
+      if (m < 0) continue;  // the filter sits this step out
+      if (st.par < 0) load_filter(st, A, ctl, f, Rp->st_in[f].parity);
+      predict(st, sh, A, f, rs.odom[e]);
+      for (int c = 0; c < m; ++c) {
+        const double z0 = rs.z[e][c][0], z1 = rs.z[e][c][1];
+        if constexpr (ASSOC) {
+          associate_correct<W, RS, CS, JOSEPH>(st, sh, A, z0, z1, c);
+        } else {
+          const int id = __builtin_amdgcn_readfirstlane(rs.ids[e][c]);
+          if (id < 0 || id >= A.N) {  // the inputs are not validated on the host
+            st.status |= EKF_FLAG_RANGE_D;
+            continue;
+          }
+          st.b ^= 1;
+          gather_rows(st, sh, A.n, st.b, 3 + 2 * id, 0);
+          __syncthreads();
+          correct<W, RS, CS, JOSEPH>(st, sh, A.r, 3 + 2 * id, z0, z1, false);
+        }
+      }
+      st.dirty = true;
+      st.post = true;  // posterior, slam.cpp:273-291 (deferred)
+      st.podom[0] = rs.odom[e][0];
+      st.podom[1] = rs.odom[e][1];
+      st.podom[2] = rs.odom[e][2];
+    }
+  }
+  // the planning state after the replay (the host adopts it lazily): the parity stays, nothing
+  // is pipelined, t_odom_robot of the last message, active or not
+  if (threadIdx.x < 64) {
+    const ResidentReplayArgs R = fetch_replay_args(Rp);
+    const PlanState& s0 = R.st_in[f];
+    PlanState& so = R.st_out[f];
+    const int lane = threadIdx.x;
+    if (lane == 0) {
+      so.parity = s0.parity;
+      so.prev_m = -1;
+      so.pending = st.par >= 0 ? 0 : s0.pending;
+      so.pad = 0;
+      so.pad2 = 0.0;
+    }
+    if (lane < kMaxChunk) so.prev_ids[lane] = s0.prev_ids[lane];
+    if (lane < 3) so.odom[lane] = R.odom[(static_cast<size_t>(R.T - 1) * R.F + f) * 3 + lane];
+  }
+  if (st.par < 0) return;  // no message for this filter
+  if (st.post) posterior_now(st, sh, A, f);
+  store_filter(st, sh, A, ctl, f);
+}
+
+hipError_t launch_resident_replay(const PassArgs<double>& a, const ResidentReplayArgs& r,
+                                  hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+  if (a.n > kResidentMaxN || r.F <= 0 || r.T <= 0 || r.M < 1 || r.M > kMaxAssoc || r.stride < 2)
+    return hipErrorInvalidValue;
+  auto go = [&](auto kernel) { launch(kernel, dim3(r.F), dim3(256), s, e0, e1, a, r); };
+  // the shapes of launch_resident; form and association are instantiations of their own, so each
+  // keeps its register budget
+  auto shape = [&](auto J, auto U) {
+    constexpr bool j = decltype(J)::value, u = decltype(U)::value;
+    if (a.n <= 64)
+      go(k_resident_replay<4, 16, 1, j, u>);
+    else if (a.n <= 4 * 26)
+      go(k_resident_replay<4, 26, 2, j, u>);
+    else
+      go(k_resident_replay<4, 32, 2, j, u>);
+  };
+  using T = std::true_type;
+  using N = std::false_type;
+  if (a.joseph)
+    r.assoc ? shape(T{}, T{}) : shape(T{}, N{});
+  else
+    r.assoc ? shape(N{}, T{}) : shape(N{}, N{});
   return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // The scheduler of the runtime behind include/ekf.h: the handle's two HIP streams and their CU
 // masks, the upload ring, and the launch sequence of a plan (ekf_plan.hpp) — host-planned (flush)
-// or written on the device (ekf_replay_device, run_device_plan).
+// or written on the device (ekf_replay_device, run_device_plan) — and the resident path's replay
+// from device inputs, which needs no plan at all (ekf_replay_resident).
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
@@ -378,6 +379,60 @@ int flush_resident(ekf_ctx* h) {
   return rc;
 }
 
+// The device replays' planning state: two device copies (ping-pong by dstate_cur) and the pinned
+// host copy, allocated at the first device replay.
+int ensure_plan_state(ekf_ctx* h) {
+  if (h->dstate[0]) return EKF_OK;
+  const size_t F = static_cast<size_t>(h->F);
+  for (PlanState*& p : h->dstate)
+    if (hipMalloc(&p, F * sizeof(PlanState)) != hipSuccess) return EKF_E_NOMEM;
+  if (hipHostMalloc(reinterpret_cast<void**>(&h->hstate), F * sizeof(PlanState),
+                    hipHostMallocDefault) != hipSuccess)
+    return EKF_E_NOMEM;
+  return EKF_OK;
+}
+
+// The host mirror goes down once, on the stream the device planner runs on; later device replays
+// chain on the device.
+int export_plan_state(ekf_ctx* h, hipStream_t ps) {
+  if (h->dev_plan) return EKF_OK;
+  h->plan.export_state(h->hstate);
+  HIPCHK(hipMemcpyAsync(h->dstate[h->dstate_cur], h->hstate, h->F * sizeof(PlanState),
+                        hipMemcpyHostToDevice, ps));
+  h->dev_plan = true;
+  return EKF_OK;
+}
+
+// A replay's odometry from the host (lm_replay_into, lm_replay_resident): `no` doubles into the
+// handle's pinned staging, once the last upload has left it (stage_odom), then onto the device on
+// the stream that reads it (upload_odom).
+int stage_odom(ekf_ctx* h, const double* host_odom, size_t no) {
+  if (!h->ev_odom) HIPCHK(hipEventCreateWithFlags(&h->ev_odom, hipEventDisableTiming));
+  if (no > h->odom_cap) {
+    if (drain(h)) return EKF_E_HIP;  // a kernel in flight may still read the old buffer
+    if (h->odom_d) HIPCHK(hipFree(h->odom_d));
+    if (h->odom_h) HIPCHK(hipHostFree(h->odom_h));
+    h->odom_d = h->odom_h = nullptr;
+    h->odom_cap = 0;
+    const size_t cap = std::max(no, static_cast<size_t>(3 * 64) * h->F);
+    if (hipMalloc(&h->odom_d, cap * sizeof(double)) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&h->odom_h), cap * sizeof(double),
+                      hipHostMallocDefault) != hipSuccess)
+      return EKF_E_NOMEM;
+    h->odom_cap = cap;
+  } else {
+    HIPCHK(hipEventSynchronize(h->ev_odom));  // the last upload has left the staging
+  }
+  std::memcpy(h->odom_h, host_odom, no * sizeof(double));
+  return EKF_OK;
+}
+
+int upload_odom(ekf_ctx* h, size_t no, hipStream_t ps) {
+  HIPCHK(hipMemcpyAsync(h->odom_d, h->odom_h, no * sizeof(double), hipMemcpyHostToDevice, ps));
+  HIPCHK(hipEventRecord(h->ev_odom, ps));
+  return EKF_OK;
+}
+
 // Deferred submission (ekf_defer): callbacks append to the plan, which goes up with ONE upload and
 // runs as one resident launch (or one pipelined run) once it is large or the caller synchronises.
 constexpr size_t kFlushDesc = 8192;
@@ -633,13 +688,7 @@ int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* 
   hipSetDevice(h->cfg.device);
   if (int rc = flush(h)) return rc;  // what the host planned before runs first
   const size_t F = static_cast<size_t>(h->F);
-  if (!h->dstate[0]) {
-    for (PlanState*& p : h->dstate)
-      if (hipMalloc(&p, F * sizeof(PlanState)) != hipSuccess) return EKF_E_NOMEM;
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->hstate), F * sizeof(PlanState),
-                      hipHostMallocDefault) != hipSuccess)
-      return EKF_E_NOMEM;
-  }
+  if (int rc = ensure_plan_state(h)) return rc;
   if (int rc = reserve_device(h, static_cast<size_t>(T) * F)) return rc;  // (no host staging)
   // device epochs: the planner runs on the bulk stream — ahead of the group's factor kernels and
   // Σ passes in stream order — and counts its descriptors, which the chain launch polls: the chain
@@ -656,12 +705,7 @@ int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* 
     h->main_unordered = false;
   }
   hipStream_t ps = beside ? h->bulk : h->stream;
-  if (!h->dev_plan) {  // the host mirror goes down once; later device replays chain on the device
-    h->plan.export_state(h->hstate);
-    HIPCHK(hipMemcpyAsync(h->dstate[h->dstate_cur], h->hstate, F * sizeof(PlanState),
-                          hipMemcpyHostToDevice, ps));
-    h->dev_plan = true;
-  }
+  if (int rc = export_plan_state(h, ps)) return rc;
   ReplayArgs a{};
   a.counts = d_counts;
   a.ids = d_ids;
@@ -705,34 +749,11 @@ int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const
   if (int rc = flush(h)) return rc;  // what the host planned before runs first
   const size_t F = static_cast<size_t>(h->F);
   const int C = (m_max + kMaxChunk - 1) / kMaxChunk;
-  if (!h->dstate[0]) {
-    for (PlanState*& p : h->dstate)
-      if (hipMalloc(&p, F * sizeof(PlanState)) != hipSuccess) return EKF_E_NOMEM;
-    if (hipHostMalloc(reinterpret_cast<void**>(&h->hstate), F * sizeof(PlanState),
-                      hipHostMallocDefault) != hipSuccess)
-      return EKF_E_NOMEM;
-  }
+  if (int rc = ensure_plan_state(h)) return rc;
   if (int rc = reserve_device(h, static_cast<size_t>(T) * C * F)) return rc;
   const size_t no = 3 * static_cast<size_t>(T) * F;
-  if (host_odom) {
-    if (!h->ev_odom) HIPCHK(hipEventCreateWithFlags(&h->ev_odom, hipEventDisableTiming));
-    if (no > h->odom_cap) {
-      if (drain(h)) return EKF_E_HIP;  // a planner in flight may still read the old buffer
-      if (h->odom_d) HIPCHK(hipFree(h->odom_d));
-      if (h->odom_h) HIPCHK(hipHostFree(h->odom_h));
-      h->odom_d = h->odom_h = nullptr;
-      h->odom_cap = 0;
-      const size_t cap = std::max(no, static_cast<size_t>(3 * 64) * F);
-      if (hipMalloc(&h->odom_d, cap * sizeof(double)) != hipSuccess ||
-          hipHostMalloc(reinterpret_cast<void**>(&h->odom_h), cap * sizeof(double),
-                        hipHostMallocDefault) != hipSuccess)
-        return EKF_E_NOMEM;
-      h->odom_cap = cap;
-    } else {
-      HIPCHK(hipEventSynchronize(h->ev_odom));  // the last upload has left the staging
-    }
-    std::memcpy(h->odom_h, host_odom, no * sizeof(double));
-  }
+  if (host_odom)
+    if (int rc = stage_odom(h, host_odom, no)) return rc;
   // The planner rewrites the upload buffer on the stream the association launches run on. Work on
   // that stream is ahead of it in stream order; work on the main stream that the bulk stream is
   // not ordered after yet (a chain, a k_posterior reading its descriptor) must end first: the hop a
@@ -740,16 +761,9 @@ int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const
   hipStream_t ps = h->serial ? h->stream : h->bulk;
   if (!h->serial && (h->main_dirty || h->main_unordered) && fork_bulk_clean(h)) return EKF_E_HIP;
   if (ready) HIPCHK(hipStreamWaitEvent(ps, ready, 0));
-  if (host_odom) {
-    HIPCHK(hipMemcpyAsync(h->odom_d, h->odom_h, no * sizeof(double), hipMemcpyHostToDevice, ps));
-    HIPCHK(hipEventRecord(h->ev_odom, ps));
-  }
-  if (!h->dev_plan) {  // the host mirror goes down once; later device replays chain on the device
-    h->plan.export_state(h->hstate);
-    HIPCHK(hipMemcpyAsync(h->dstate[h->dstate_cur], h->hstate, F * sizeof(PlanState),
-                          hipMemcpyHostToDevice, ps));
-    h->dev_plan = true;
-  }
+  if (host_odom)
+    if (int rc = upload_odom(h, no, ps)) return rc;
+  if (int rc = export_plan_state(h, ps)) return rc;
   AssocReplayArgs a{};
   a.counts = d_counts;
   a.xy = d_xy;
@@ -775,6 +789,52 @@ int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const
   return rc;
 }
 
+// Resident path: T messages whose inputs are in device memory, walked by ONE launch of
+// k_resident_replay (ekf_resident.hip) on the main stream, the only stream a resident handle
+// uses: no descriptors, no planner kernel. The planning state goes through the device copies as
+// in the two replays above (the kernel leaves st_out), so adopt_device_plan works unchanged.
+// host_odom / ready as replay_device_assoc's; consumed (nullable) is recorded behind the kernel,
+// which reads its inputs for the whole launch.
+int replay_resident(ekf_ctx* h, int assoc, int T, int m_max, const int* d_counts, const int* d_ids,
+                    const int* d_actions, const double* d_xy, int xy_stride, const double* d_odom,
+                    const double* host_odom, hipEvent_t ready, hipEvent_t consumed) {
+  hipSetDevice(h->cfg.device);
+  if (int rc = flush(h)) return rc;  // what the host planned before runs first
+  if (int rc = ensure_plan_state(h)) return rc;
+  const size_t no = 3 * static_cast<size_t>(T) * h->F;
+  if (host_odom)
+    if (int rc = stage_odom(h, host_odom, no)) return rc;
+  hipStream_t ps = h->stream;
+  if (ready) HIPCHK(hipStreamWaitEvent(ps, ready, 0));
+  if (host_odom)
+    if (int rc = upload_odom(h, no, ps)) return rc;
+  if (int rc = export_plan_state(h, ps)) return rc;
+  ResidentReplayArgs r{};
+  r.counts = d_counts;
+  r.ids = assoc ? nullptr : d_ids;
+  r.actions = assoc ? nullptr : d_actions;
+  r.xy = d_xy;
+  r.odom = host_odom ? h->odom_d : d_odom;
+  r.st_in = h->dstate[h->dstate_cur];
+  r.st_out = h->dstate[h->dstate_cur ^ 1];
+  r.T = T;
+  r.F = h->F;
+  r.M = m_max;
+  r.stride = xy_stride;
+  r.assoc = assoc ? 1 : 0;
+  const PassArgs<double> a = args<double>(h, nullptr, 0);
+  const int rc = timed(h, kProfResident, [&](hipEvent_t e0, hipEvent_t e1) {
+    return launch_resident_replay(a, r, ps, e0, e1);
+  });
+  // (a failed launch leaves dstate_cur where it is: the copy export_plan_state just wrote is the
+  // one a later adopt_device_plan reads back, so the handle goes on from the state before the call)
+  if (rc) return rc;
+  if (consumed) HIPCHK(hipEventRecord(consumed, ps));
+  h->dstate_cur ^= 1;
+  h->plan_stream = ps;
+  return EKF_OK;
+}
+
 int replay_markers(ekf_t h, int device, int T, int m_max, const int* d_counts,
                    const double* d_markers, const double* odom, hipEvent_t ready,
                    hipEvent_t planned) {
@@ -782,6 +842,16 @@ int replay_markers(ekf_t h, int device, int T, int m_max, const int* d_counts,
       !d_markers || !odom || !device_assoc_supported(h))
     return EKF_E_ARG;
   return replay_device_assoc(h, T, m_max, d_counts, d_markers, 4, nullptr, odom, ready, planned);
+}
+
+int replay_markers_resident(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                            const double* d_markers, const double* odom, hipEvent_t ready,
+                            hipEvent_t consumed) {
+  if (!h || device != h->cfg.device || T < 1 || m_max < 1 || m_max > kMaxAssoc || !d_counts ||
+      !d_markers || !odom || !h->resident)
+    return EKF_E_ARG;
+  return replay_resident(h, 1, T, m_max, d_counts, nullptr, nullptr, d_markers, 4, nullptr, odom,
+                         ready, consumed);
 }
 
 int handle_info(ekf_t h, HandleInfo* out) {

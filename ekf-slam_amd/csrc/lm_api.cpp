@@ -2,7 +2,8 @@
 // laserCallback (nuslam/src/landmarks.cpp:109-156) over lm_kernels.hip, and the simulated laser
 // (nusim/src/nusim.cpp:559-710) over lidar_kernels.hip whose scans it can detect on in place.
 // lm_detect_device leaves the markers on the device, and lm_replay_into hands them to a filter
-// handle's device planner (k_plan_assoc) without a host hop.
+// handle's device planner (k_plan_assoc) without a host hop; lm_replay_resident to a resident
+// handle's replay kernel, which reads them in place.
 #include <hip/hip_runtime.h>
 
 #include <new>
@@ -339,6 +340,21 @@ int lm_replay_into(lm_t h, ekf_t e, int T, const double* odom) {
                                          reinterpret_cast<const double*>(h->d_markers), odom,
                                          h->e_det, h->e_planned);
   // (an argument error comes back before anything is enqueued; past that the planner may be)
+  if (rc != EKF_E_ARG) h->planner_reads = true;
+  return rc;
+}
+
+int lm_replay_resident(lm_t h, ekf_t e, int T, const double* odom) {
+  if (!h || !e || T < 1 || !odom || h->dev_scans <= 0) return EKF_E_ARG;
+  int F = 0;
+  if (ekf_dims(e, nullptr, nullptr, &F) != EKF_OK || F < 1 ||
+      static_cast<long long>(T) * F != h->dev_scans || h->dev_cap > 64)
+    return EKF_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  // the filter's kernel reads the markers in place throughout: e_planned sits behind it
+  const int rc = ekfslam::replay_markers_resident(e, h->device, T, h->dev_cap, h->d_counts,
+                                                  reinterpret_cast<const double*>(h->d_markers),
+                                                  odom, h->e_det, h->e_planned);
   if (rc != EKF_E_ARG) h->planner_reads = true;
   return rc;
 }

@@ -32,7 +32,7 @@ EXPORTS = [
     "ekf_get_assoc_route", "ekf_get_schedule",
     "ekf_set_odom",
     "ekf_fake_sensor", "ekf_sensor", "ekf_batch_sensor", "ekf_replay", "ekf_replay_device",
-    "ekf_replay_device_assoc", "ekf_get_decisions",
+    "ekf_replay_device_assoc", "ekf_replay_resident", "ekf_get_decisions",
     "ekf_predict",
     "ekf_correct", "ekf_associate_correct", "ekf_posterior", "ekf_sync", "ekf_flush", "ekf_get_pose",
     "ekf_get_map_odom", "ekf_get_state", "ekf_set_state", "ekf_get_status", "ekf_defer",
@@ -46,12 +46,14 @@ EXPORTS = [
     "lm_create", "lm_destroy", "lm_detect", "lm_fit_circles", "lm_check_circles",
     "lm_last_kernel_us",
     "lm_scan_config_default", "lm_simulate", "lm_detect_resident", "lm_last_simulate_us",
-    "lm_detect_device", "lm_fetch_markers", "lm_replay_into",
+    "lm_detect_device", "lm_fetch_markers", "lm_replay_into", "lm_replay_resident",
     "ekf_sim_config_default", "ekf_sim_create", "ekf_sim_destroy", "ekf_sim_run",
     "ekf_sim_markers", "ekf_sim_poses",
 ]
 TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear",
                  "slam_replay_trace")
+# what a library built from an earlier commit (EKF_LIB, the A/B tools) may lack
+LATER_EXPORTS = TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident")
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
 
 
@@ -121,6 +123,7 @@ def lib():
             "ekf_replay": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
             "ekf_replay_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
             "ekf_replay_device_assoc": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp]),
+            "ekf_replay_resident": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
             "ekf_get_decisions": (_i, [_vp, _i, _i, _vp, _vp]),
             "ekf_predict": (_i, [_vp, _i]),
             "ekf_correct": (_i, [_vp, _i, _i, _d, _d]),
@@ -170,6 +173,7 @@ def lib():
             "lm_detect_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _d, _i]),
             "lm_fetch_markers": (_i, [_vp, _vp, _i, _vp]),
             "lm_replay_into": (_i, [_vp, _vp, _i, _vp]),
+            "lm_replay_resident": (_i, [_vp, _vp, _i, _vp]),
             "ekf_sim_config_default": (None, [C.POINTER(SimConfig)]),
             "ekf_sim_create": (_i, [C.POINTER(_vp), _vp, C.POINTER(SimConfig), _i, _vp]),
             "ekf_sim_destroy": (_i, [_vp]),
@@ -179,8 +183,9 @@ def lib():
         }
         for name, (res, argt) in sig.items():
             # (EKF_LIB naming a library built from an earlier commit, for the A/B tools: it loads
-            # without the pose trace, and a call of it fails; build() checks EXPORTS)
-            if name in TRACE_EXPORTS and not hasattr(L, name):
+            # without the pose trace or the resident device replays, and a call of one fails;
+            # build() checks EXPORTS)
+            if name in LATER_EXPORTS and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -329,6 +334,40 @@ class EKF:
         """ekf_replay_device_assoc on raw device addresses (ints); returns the status code."""
         return lib().ekf_replay_device_assoc(self.h, T, M, counts or None, xy or None, stride,
                                              odom or None)
+
+    def replay_resident(self, counts, xy, odom, ids=None, actions=None, stride=None):
+        """ekf_replay_resident: a replay on a resident handle whose inputs are GPU tensors already
+        on this handle's device, run by one kernel launch — counts [T,F] int32 (<= 0: no message),
+        xy [T,F,M,2] float64 (packed pairs) or [T,F,M,4] (lm_marker rows: x, y first), odom [T,F,3]
+        float64; M <= 64. ``ids`` [T,F,M] int32 (and optionally ``actions``): known ids; ``ids``
+        None: unknown association. ``stride``: doubles between markers, by default xy.shape[-1].
+        Asynchronous; keep the tensors alive until a sync."""
+        import torch
+        T, M = int(xy.shape[0]), int(xy.shape[2])
+        stride = int(xy.shape[-1]) if stride is None else int(stride)
+        rc = self.replay_resident_raw(int(ids is None), T, M, _dptr(counts, torch.int32),
+                                      _dptr(ids, torch.int32), _dptr(actions, torch.int32),
+                                      _dptr(xy, torch.float64), stride,
+                                      _dptr(odom, torch.float64))
+        _check(rc, "ekf_replay_resident")
+
+    def replay_resident_raw(self, assoc, T, M, counts, ids, actions, xy, stride, odom):
+        """ekf_replay_resident on raw device addresses (ints, 0 / None: NULL); returns the status
+        code."""
+        return lib().ekf_replay_resident(self.h, int(assoc), T, M, counts or None, ids or None,
+                                         actions or None, xy or None, stride, odom or None)
+
+    def replay_on_device(self, counts, xy, odom, ids=None, actions=None, stride=None):
+        """A replay from GPU tensors by whichever entry point this handle's path has: resident
+        handles ``replay_resident``; pipeline handles ``replay_device`` (known ``ids``, packed xy,
+        M <= 16) or ``replay_device_assoc`` (``ids`` None)."""
+        if self.path == EKF_PATH_RESIDENT:
+            return self.replay_resident(counts, xy, odom, ids=ids, actions=actions, stride=stride)
+        if ids is None:
+            return self.replay_device_assoc(counts, xy, odom, stride=stride)
+        if (int(xy.shape[-1]) if stride is None else int(stride)) != 2:
+            raise ValueError("a pipeline handle's known-id replay takes packed (x, y) pairs")
+        return self.replay_device(counts, xy, odom, ids, actions)
 
     def decisions(self, m, f=0):
         """ekf_get_decisions: (assoc [m], is_new [m]) of filter f's most recent unknown-association

@@ -163,6 +163,14 @@ class Detector:
             raise ValueError("odom must be [T, F, 3]")
         return lib().lm_replay_into(self.h, ekf.h, T, od.ctypes.data)
 
+    def replay_resident(self, ekf, T, odom):
+        """lm_replay_resident: ``replay_into`` for a resident filter handle (one kernel launch
+        reads the markers in place). Returns the status code."""
+        od = np.ascontiguousarray(odom, dtype=np.float64)
+        if od.size != 3 * T * ekf.F:
+            raise ValueError("odom must be [T, F, 3]")
+        return lib().lm_replay_resident(self.h, ekf.h, T, od.ctypes.data)
+
     def last_simulate_us(self):
         us = C.c_double()
         _check(lib().lm_last_simulate_us(self.h, C.byref(us)), "lm_last_simulate_us")

@@ -164,7 +164,8 @@ int ekf_replay(ekf_t h, int assoc, int T, int m_max, const int* counts, const in
  * Inputs are not validated on the host: an id outside [0, N) is skipped by the correction and
  * sets EKF_FLAG_RANGE in the filter's status. Asynchronous; the inputs must stay valid until the
  * next synchronising call (ekf_sync, a state read). The handle's planning state comes back to the
- * host at the next host-planned call or state access. */
+ * host at the next host-planned call or state access.
+ * A resident handle (EKF_PATH_RESIDENT) takes ekf_replay_resident with assoc = 0 instead. */
 int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int* d_ids,
                       const int* d_actions, const double* d_rel_xy, const double* d_odom);
 
@@ -191,15 +192,52 @@ int ekf_replay_device(ekf_t h, int T, int m_max, const int* d_counts, const int*
  * than needed. Asynchronous; the inputs must stay valid until the next synchronising call
  * (ekf_sync, a state read). A full map and skipped markers are reported through ekf_get_status.
  * The handle's planning state comes back to the host at the next host-planned call or state
- * access. */
+ * access.
+ * A resident handle (EKF_PATH_RESIDENT) takes ekf_replay_resident with assoc = 1 instead. */
 int ekf_replay_device_assoc(ekf_t h, int T, int m_max, const int* d_counts, const double* d_xy,
                             int xy_stride, const double* d_odom);
+
+/* Resident handles only (EKF_PATH_RESIDENT; a pipeline handle: EKF_E_ARG, it has ekf_replay_device
+ * and ekf_replay_device_assoc). T messages per filter whose inputs already live on the handle's
+ * GPU, run by ONE kernel launch, no descriptors, nothing crosses PCIe. assoc = 0: known ids
+ * (d_ids required, d_actions nullable); assoc = 1: unknown association (d_ids/d_actions ignored).
+ * 1 <= m_max <= 64, T >= 1, xy_stride >= 2. Either form (ekf_set_joseph). Asynchronous.
+ *   d_counts  [T][F] int. A count <= 0 is no message: nothing of the filter changes (it is not
+ *             even loaded if the whole replay holds no message for it). A count above m_max is
+ *             clamped to m_max. Known ids: a message whose first min(count, m_max) markers are
+ *             all DELETE is a predict + posterior (slam.cpp:205).
+ *   d_ids, d_actions  [T][F][m_max] int, known ids only. Not validated on the host: an id outside
+ *             [0, N) is skipped by the correction and sets EKF_FLAG_RANGE in the filter's status.
+ *             A first sighting initialises its landmark (slam.cpp:213-216).
+ *   d_xy      marker i of message t of filter f is the two doubles at
+ *             d_xy[((t*F + f)*m_max + i)*xy_stride + {0, 1}], as ekf_replay_device_assoc's:
+ *             xy_stride = 2 is rel_xy[T][F][m_max][2], 4 an lm_marker array read in place.
+ *   d_odom    [T][F][3], t_odom_robot per message.
+ * The measurement (range, bearing) of slam.cpp:208-210 / :346-347 is computed on the GPU, for both
+ * kinds alike: the range x*x + y*y rounded product by product and a correctly rounded sqrt, the
+ * bearing's atan2 in double-double arithmetic rounded once, so it differs from a host-planned
+ * replay's only in the last bit and only where glibc's atan2 is not the correctly rounded value
+ * (about one argument in a thousand).
+ * Unknown association: marker i's decision lands in slot i (ekf_get_decisions shows the last
+ * message's); a marker that meets a full map is skipped with decision -1 and EKF_FLAG_RANGE.
+ * Skipped markers (EKF_FLAG_RANGE, EKF_FLAG_NUMERIC) are reported through ekf_get_status only.
+ * The pose trace gets one record per message with count > 0, as from any other entry point.
+ * EKF_E_ARG, and nothing changes: a NULL handle / d_counts / d_xy / d_odom, assoc = 0 with a NULL
+ * d_ids, T < 1, m_max outside [1, 64], xy_stride < 2, a pipeline handle.
+ * What the host planned before (deferred calls included) is submitted first. The inputs must stay
+ * valid until the next synchronising call (ekf_sync, a state read): the kernel reads them
+ * throughout. The handle's planning state comes back to the host at the next host-planned call
+ * or state access; a later call of any kind continues from the state the replay left. */
+int ekf_replay_resident(ekf_t h, int assoc, int T, int m_max, const int* d_counts,
+                        const int* d_ids, const int* d_actions, const double* d_xy,
+                        int xy_stride, const double* d_odom);
 
 /* The decisions (slam.cpp:344-440) of `filter`'s most recent unknown-association message, its
  * first m <= 64 markers: assoc_out[i] = landmark slot, or -1 when the marker met a full map;
  * is_new_out[i] = 1 when it opened that slot. Either output may be NULL. After ekf_sensor,
- * ekf_batch_sensor / ekf_replay with assoc = 1, ekf_replay_device_assoc or lm_replay_into; markers
- * beyond the message's own count hold an earlier message's decisions. Synchronises. */
+ * ekf_batch_sensor / ekf_replay with assoc = 1, ekf_replay_device_assoc, ekf_replay_resident with
+ * assoc = 1, lm_replay_into or lm_replay_resident; markers beyond the message's own count hold an
+ * earlier message's decisions. Synchronises. */
 int ekf_get_decisions(ekf_t h, int filter, int m, int* assoc_out, int* is_new_out);
 
 /* ---- the finer-grained surface (north_star: predict()/update()/associate()) ---- */
@@ -266,10 +304,11 @@ int ekf_get_status(ekf_t h, int filter, unsigned* flags); /* and clears them */
  *     bit, with the same launches.
  *   One record per posterior: a filter gets a record wherever a kernel stores its t_map_odom, i.e.
  *     once per message, in whichever form it arrived (ekf_fake_sensor, ekf_sensor,
- *     ekf_batch_sensor, ekf_replay, ekf_replay_device, ekf_replay_device_assoc, lm_replay_into,
- *     ekf_sim_run; deferred or not), and once per ekf_posterior. A message a filter sits out
- *     (count <= 0) appends nothing; a message whose markers are all DELETE (predict + posterior)
- *     appends one; a message split over several chunks appends one, from its last chunk.
+ *     ekf_batch_sensor, ekf_replay, ekf_replay_device, ekf_replay_device_assoc,
+ *     ekf_replay_resident, lm_replay_into, lm_replay_resident, ekf_sim_run; deferred or not),
+ *     and once per ekf_posterior. A message a filter sits out (count <= 0) appends nothing; a
+ *     message whose markers are all DELETE (predict + posterior) appends one; a message split over
+ *     several chunks appends one, from its last chunk.
  *   Beyond `capacity`, records are counted, not written (as lm_detect counts the markers beyond
  *     max_markers): ekf_trace_count returns how many were appended, ekf_trace_read copies
  *     [first, first + n) ∩ [0, min(appended, capacity)) and sets *got to how many that is.

@@ -122,8 +122,14 @@ int lm_fetch_markers(lm_t h, lm_marker* markers, int max_markers, int* counts);
  * the detection, and the handle's next detect waits on the device until the filter has planned
  * from the marker buffer: asynchronous on both handles, nothing crosses PCIe but odom.
  * EKF_E_ARG: nothing detected yet, T*F != n_scans, max_markers > 64, handles on different
- * devices, or a filter handle ekf_replay_device_assoc refuses. */
+ * devices, or a filter handle ekf_replay_device_assoc refuses (a resident one: it has
+ * lm_replay_resident). */
 int lm_replay_into(lm_t h, ekf_t e, int T, const double* odom);
+/* lm_replay_into for a resident filter handle: same contract otherwise. The messages run as
+ * ekf_replay_resident with assoc = 1 (ekf.h), one kernel launch that reads the marker buffer in
+ * place throughout, so the handle's next detect waits on the device until that kernel has ended.
+ * EKF_E_ARG: what lm_replay_into lists, with "a pipeline filter handle" for its last item. */
+int lm_replay_resident(lm_t h, ekf_t e, int T, const double* odom);
 
 #ifdef __cplusplus
 }
