@@ -1,11 +1,13 @@
 // The C ABI of include/ekf.h: argument checks, the message into the planner (ekf_plan.hpp), then
 // the scheduler (ekf_sched.cpp). ekf_create / ekf_destroy own the handle's device resources.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <new>
 #include <vector>
 
 #include "ekf_ctx.hpp"
+#include "ekf_internal.hpp"
 #include "geom.hpp"
 
 using namespace ekfslam;
@@ -26,7 +28,99 @@ int load_and_plan(ekf_ctx* h, int assoc_mode, int m_max, const int* counts, cons
   return EKF_OK;
 }
 
+// ---- gather and score (ekf_eval.hip): one device buffer per call, carved 16 bytes at a time ----
+
+size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
+
+int eval_reserve(ekf_ctx* h, size_t bytes) {
+  if (bytes <= h->eval_cap) return EKF_OK;
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();  // (the launchers return hipGetLastError())
+    return EKF_E_NOMEM;
+  }
+  if (h->eval_buf) hipFree(h->eval_buf);
+  h->eval_buf = p;
+  h->eval_cap = bytes;
+  return EKF_OK;
+}
+
+// The planner's parity of every filter (valid after settle(): a device replay's planning state
+// has been adopted) into d_par, and the launch arguments over it.
+int eval_args(ekf_ctx* h, int* d_par, int f0, EvalArgs* a) {
+  std::vector<int> par(h->F);
+  for (int f = 0; f < h->F; ++f) par[f] = h->plan.parity(f);
+  HIPCHK(hipMemcpy(d_par, par.data(), par.size() * sizeof(int), hipMemcpyHostToDevice));
+  *a = EvalArgs{};
+  for (int p = 0; p < 2; ++p) {
+    a->sig[p] = h->sig[p];
+    a->x[p] = h->x[p];
+  }
+  a->sig_stride = h->sig_stride;
+  a->x_stride = h->x_stride;
+  a->ctl = h->ctl;
+  a->parity = d_par;
+  a->N = h->cfg.n_landmarks;
+  a->ld = h->ld;
+  a->f0 = f0;
+  return EKF_OK;
+}
+
+// ekf_eval: the truth from the host (h_pose [F][3], h_lm [F][n_map][2]) or, with h_pose NULL,
+// from the device (d_pose / d_lm). Arguments checked by the callers.
+int eval_run(ekf_ctx* h, const double* h_pose, const double* h_lm, const double* d_pose,
+             size_t pose_stride, const double* d_lm, int n_map, const double* frame,
+             ekf_eval_rec* out) {
+  if (int rc = settle(h)) return rc;
+  hipSetDevice(h->cfg.device);
+  const size_t F = static_cast<size_t>(h->F);
+  const size_t par_b = up16(F * sizeof(int)), rec_b = F * sizeof(EvalRec);
+  const size_t pose_b = h_pose ? up16(F * 3 * sizeof(double)) : 0;
+  const size_t lm_b = h_pose && n_map > 0 ? up16(F * n_map * 2 * sizeof(double)) : 0;
+  if (int rc = eval_reserve(h, par_b + rec_b + pose_b + lm_b)) return rc;
+  char* base = static_cast<char*>(h->eval_buf);
+  int* par = reinterpret_cast<int*>(base);
+  EvalRec* rec = reinterpret_cast<EvalRec*>(base + par_b);
+  EvalTruth t{};
+  if (h_pose) {
+    double* up = reinterpret_cast<double*>(base + par_b + rec_b);
+    HIPCHK(hipMemcpy(up, h_pose, F * 3 * sizeof(double), hipMemcpyHostToDevice));
+    d_pose = up;
+    pose_stride = 3;
+    d_lm = nullptr;
+    if (n_map > 0) {
+      double* ul = reinterpret_cast<double*>(base + par_b + rec_b + pose_b);
+      HIPCHK(hipMemcpy(ul, h_lm, F * n_map * 2 * sizeof(double), hipMemcpyHostToDevice));
+      d_lm = ul;
+    }
+  }
+  t.pose = d_pose;
+  t.pose_stride = pose_stride;
+  t.lm = n_map > 0 ? d_lm : nullptr;
+  t.n_map = n_map;
+  t.has_frame = frame != nullptr;
+  for (int k = 0; k < 3; ++k) t.frame[k] = frame ? frame[k] : 0.0;
+  EvalArgs a;
+  if (int rc = eval_args(h, par, 0, &a)) return rc;
+  HIPCHK(by_dtype(h, [&](auto tag) {
+    return launch_eval<decltype(tag)>(a, t, rec, h->F, h->stream);
+  }));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(out, rec, rec_b, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+bool eval_args_ok(const ekf_ctx* h, const void* pose, const void* lm, int n_map, const void* out) {
+  return h && pose && out && n_map >= 0 && n_map <= h->cfg.n_landmarks && (lm || n_map == 0);
+}
+
 }  // namespace
+
+int ekfslam::eval_device(ekf_t h, const double* d_pose, size_t pose_stride, const double* d_lm,
+                         int n_map, const double* frame, ekf_eval_rec* out) {
+  if (!eval_args_ok(h, d_pose, d_lm, n_map, out)) return EKF_E_ARG;
+  return eval_run(h, nullptr, nullptr, d_pose, pose_stride, d_lm, n_map, frame, out);
+}
 
 extern "C" {
 
@@ -181,6 +275,7 @@ int ekf_destroy(ekf_t h) {
   if (h->ddesc) hipFree(h->ddesc);
   if (h->trace) hipFree(h->trace);
   if (h->trace_n) hipFree(h->trace_n);
+  if (h->eval_buf) hipFree(h->eval_buf);
   for (PlanState* p : h->dstate)
     if (p) hipFree(p);
   if (h->hstate) hipHostFree(h->hstate);
@@ -608,6 +703,76 @@ int ekf_get_status(ekf_t h, int f, unsigned* flags) {
   HIPCHK(hipMemcpy(&h->ctl[f].status, &z, sizeof(unsigned), hipMemcpyHostToDevice));
   *flags |= h->held[f];
   h->held[f] = 0;
+  return EKF_OK;
+}
+
+// ---- marginals and scoring: read-only kernels over the filters' "in" copies (ekf_eval.hip) ----
+
+int ekf_get_marginals(ekf_t h, int f, double* pose, double* pose_cov, ekf_lm_marginal* lm,
+                      unsigned* counter) {
+  if (!h || f >= h->F) return EKF_E_ARG;
+  if (int rc = settle(h)) return rc;
+  hipSetDevice(h->cfg.device);
+  const int f0 = f < 0 ? 0 : f;
+  const size_t nf = f < 0 ? h->F : 1, N = h->cfg.n_landmarks;
+  const size_t par_b = up16(h->F * sizeof(int)), pose_b = up16(nf * 3 * sizeof(double)),
+               cov_b = up16(nf * 9 * sizeof(double)), cnt_b = up16(nf * sizeof(unsigned)),
+               lm_b = lm ? nf * N * sizeof(LmMarginal) : 0;
+  if (int rc = eval_reserve(h, par_b + pose_b + cov_b + cnt_b + lm_b)) return rc;
+  char* base = static_cast<char*>(h->eval_buf);
+  MarginalOut o{};
+  o.pose = reinterpret_cast<double*>(base + par_b);
+  o.pose_cov = reinterpret_cast<double*>(base + par_b + pose_b);
+  o.counter = reinterpret_cast<unsigned*>(base + par_b + pose_b + cov_b);
+  o.lm = lm ? reinterpret_cast<LmMarginal*>(base + par_b + pose_b + cov_b + cnt_b) : nullptr;
+  EvalArgs a;
+  if (int rc = eval_args(h, reinterpret_cast<int*>(base), f0, &a)) return rc;
+  HIPCHK(by_dtype(h, [&](auto tag) {
+    return launch_marginals<decltype(tag)>(a, o, static_cast<int>(nf), h->stream);
+  }));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (pose) HIPCHK(hipMemcpy(pose, o.pose, nf * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  if (pose_cov)
+    HIPCHK(hipMemcpy(pose_cov, o.pose_cov, nf * 9 * sizeof(double), hipMemcpyDeviceToHost));
+  if (counter)
+    HIPCHK(hipMemcpy(counter, o.counter, nf * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (lm) HIPCHK(hipMemcpy(lm, o.lm, lm_b, hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+int ekf_eval(ekf_t h, const double* truth_pose, const double* truth_lm, int n_map,
+             const double* frame, ekf_eval_rec* out) {
+  if (!eval_args_ok(h, truth_pose, truth_lm, n_map, out)) return EKF_E_ARG;
+  return eval_run(h, truth_pose, truth_lm, nullptr, 0, nullptr, n_map, frame, out);
+}
+
+int ekf_eval_summary(const ekf_eval_rec* recs, int nf, ekf_eval_sum* out) {
+  if (!recs || !out || nf < 1) return EKF_E_ARG;
+  const double chi2_3_95 = 7.814727903251179, nan = std::nan("");
+  double nees = 0.0, pos_sq = 0.0, head_sq = 0.0, lm_sq = 0.0, lm_nees = 0.0;
+  long long n_pose = 0, in_95 = 0, n_eval = 0, n_nees = 0;
+  for (int i = 0; i < nf; ++i) {
+    const ekf_eval_rec& r = recs[i];
+    if (std::isfinite(r.pose_nees)) {
+      n_pose += 1;
+      nees += r.pose_nees;
+      in_95 += r.pose_nees <= chi2_3_95;
+    }
+    head_sq += r.pose_err[0] * r.pose_err[0];
+    pos_sq += r.pose_err[1] * r.pose_err[1] + r.pose_err[2] * r.pose_err[2];
+    lm_sq += r.lm_sq_err;
+    lm_nees += r.lm_nees;
+    n_eval += r.n_eval;
+    n_nees += r.n_nees;
+  }
+  out->n = nf;
+  out->n_pose_nees = static_cast<int>(n_pose);
+  out->anees_pose = n_pose ? nees / n_pose : nan;
+  out->pose_in_95 = n_pose ? static_cast<double>(in_95) / n_pose : nan;
+  out->pos_rmse = std::sqrt(pos_sq / nf);
+  out->heading_rmse = std::sqrt(head_sq / nf);
+  out->lm_rmse = n_eval ? std::sqrt(lm_sq / n_eval) : nan;
+  out->anees_lm = n_nees ? lm_nees / n_nees : nan;
   return EKF_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "ekf_device.hpp"
 #include "ekf_launch.hpp"
 #include "ekf_plan.hpp"
+#include "eval_math.hpp"
 
 namespace ekfslam {
 
@@ -44,6 +45,19 @@ static_assert(sizeof(ekf_trace_rec) == sizeof(ekfslam::TraceRec) &&
                   offsetof(ekf_trace_rec, map_odom) == offsetof(ekfslam::TraceRec, map_odom) &&
                   offsetof(ekf_trace_rec, seq) == offsetof(ekfslam::TraceRec, seq),
               "ekf.h's trace record is the device's");
+static_assert(sizeof(ekf_eval_rec) == sizeof(ekfslam::EvalRec) &&
+                  offsetof(ekf_eval_rec, pose_cov) == offsetof(ekfslam::EvalRec, pose_cov) &&
+                  offsetof(ekf_eval_rec, pose_nees) == offsetof(ekfslam::EvalRec, pose_nees) &&
+                  offsetof(ekf_eval_rec, lm_var_trace) == offsetof(ekfslam::EvalRec, lm_var_trace) &&
+                  offsetof(ekf_eval_rec, n_seen) == offsetof(ekfslam::EvalRec, n_seen) &&
+                  offsetof(ekf_eval_rec, flags) == offsetof(ekfslam::EvalRec, flags),
+              "ekf.h's eval record is the device's");
+static_assert(sizeof(ekf_lm_marginal) == sizeof(ekfslam::LmMarginal) &&
+                  offsetof(ekf_lm_marginal, cov) == offsetof(ekfslam::LmMarginal, cov) &&
+                  offsetof(ekf_lm_marginal, seen) == offsetof(ekfslam::LmMarginal, seen),
+              "ekf.h's landmark marginal is the device's");
+static_assert(EKF_EVAL_POSE_NOT_PD == ekfslam::kEvalPoseNotPd &&
+                  EKF_EVAL_LM_NOT_PD == ekfslam::kEvalLmNotPd, "ekf.h and eval_math.hpp agree");
 
 struct ekf_ctx {
   ekf_config cfg{};
@@ -89,6 +103,10 @@ struct ekf_ctx {
   ekfslam::TraceRec* trace = nullptr;  // [F][trace_cap]
   long long* trace_n = nullptr;        // [F] records appended
   int trace_cap = 0;
+  // ekf_get_marginals / ekf_eval: one device buffer for a call's inputs and outputs (grown, never
+  // shrunk; freed with the handle)
+  void* eval_buf = nullptr;
+  size_t eval_cap = 0;
   size_t sig_stride = 0, x_stride = 0, km_stride = 0;
   // ekf_replay_device: the planning state lives on the device while dev_plan (ping-pong by
   // dstate_cur); the planner adopts it (adopt_device_plan) before it is used again

@@ -46,4 +46,10 @@ int replay_markers_resident(ekf_t h, int device, int T, int m_max, const int* d_
                             const double* d_markers, const double* odom, hipEvent_t ready,
                             hipEvent_t consumed);
 
+// ekf_eval with the truth already on the handle's device (ekf_sim_eval): filter f's true pose at
+// d_pose[f·pose_stride], its map d_lm[F][n_map][2] (nullable with n_map = 0), frame[3] nullable.
+// Synchronises like ekf_get_*; out[F] on the host. EKF_E_ARG as ekf_eval's.
+int eval_device(ekf_t h, const double* d_pose, size_t pose_stride, const double* d_lm, int n_map,
+                const double* frame, ekf_eval_rec* out);
+
 }  // namespace ekfslam

@@ -204,6 +204,40 @@ struct AssocReplayArgs {
 };
 hipError_t launch_plan_assoc(const AssocReplayArgs& a, hipStream_t s);
 
+// Gather and score (ekf_eval.hip; ekf_get_marginals, ekf_eval, ekf_sim_eval): one workgroup per
+// filter [f0, f0 + n_filters) reads the pose block and the N diagonal 2×2 blocks of the filter's
+// "in" Σ copy and its state; output k belongs to filter f0 + k. Nothing of the handle is written.
+struct LmMarginal;  // eval_math.hpp
+struct EvalRec;
+struct EvalArgs {
+  const void* sig[2];     // Σ ping-pong copies, filter 0 (fp64 or fp32: the launcher's T)
+  size_t sig_stride;      // elements between filters
+  const double* x[2];
+  size_t x_stride;
+  const FilterCtl* ctl;
+  const int* parity;      // [F]: the copy each filter's next chunk would read
+  int N, ld, f0;
+};
+struct MarginalOut {      // each nullable
+  double* pose;           // [n_filters][3]
+  double* pose_cov;       // [n_filters][9] row-major
+  LmMarginal* lm;         // [n_filters][N]
+  unsigned* counter;      // [n_filters]
+};
+struct EvalTruth {
+  const double* pose;     // filter f's (θ, x, y) at pose[f·pose_stride]
+  size_t pose_stride;     // doubles between filters
+  const double* lm;       // [F][n_map][2], NaN: no truth for the slot (nullptr with n_map = 0)
+  int n_map;
+  int has_frame;          // 0: the truth is in the map frame already, no transform at all
+  double frame[3];        // (θ0, x0, y0): the map frame's pose in the truth's frame
+};
+template <typename T>
+hipError_t launch_marginals(const EvalArgs& a, const MarginalOut& o, int n_filters, hipStream_t s);
+template <typename T>
+hipError_t launch_eval(const EvalArgs& a, const EvalTruth& t, EvalRec* out, int n_filters,
+                       hipStream_t s);
+
 // Σ₀ diagonal: Σ[i][i] = v for i ≥ 3 (the rest is zero-filled by the caller).
 template <typename T>
 hipError_t launch_init_diag(T* sig, size_t stride, int n, int ld, double v, int nf, hipStream_t s);

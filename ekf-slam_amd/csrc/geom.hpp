@@ -9,7 +9,16 @@
 //   DiffDrive::fkin   turtlelib/src/diff_drive.cpp:10-28
 //   DiffDrive::ikin   turtlelib/src/diff_drive.cpp:30-38  (host only; throws on lateral twist)
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#else  // the host compiler alone (eval_math.hpp under tests/eval_math_host_main.cpp)
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#endif
 
 #include <cmath>
 

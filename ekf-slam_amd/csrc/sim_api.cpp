@@ -411,4 +411,15 @@ int ekf_sim_poses(ekf_sim_t s, double* odom, double* truth) {
   return EKF_OK;
 }
 
+int ekf_sim_eval(ekf_sim_t s, ekf_eval_rec* out) {
+  if (!s || !out) return EKF_E_ARG;
+  hipSetDevice(s->info.device);
+  // SimState::truth is final once the simulator's stream is idle (the filter's own work is waited
+  // for by the evaluation, like any state read)
+  if (hipStreamSynchronize(s->sst) != hipSuccess) return EKF_E_HIP;
+  const double frame[3] = {s->cfg.start_theta, s->cfg.start_x, s->cfg.start_y};
+  return eval_device(s->h, s->st->truth, sizeof(SimState) / sizeof(double), s->lm, s->L, frame,
+                     out);
+}
+
 }  // extern "C"

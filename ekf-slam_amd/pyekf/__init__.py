@@ -49,11 +49,14 @@ EXPORTS = [
     "lm_detect_device", "lm_fetch_markers", "lm_replay_into", "lm_replay_resident",
     "ekf_sim_config_default", "ekf_sim_create", "ekf_sim_destroy", "ekf_sim_run",
     "ekf_sim_markers", "ekf_sim_poses",
+    "ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval",
 ]
 TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear",
                  "slam_replay_trace")
 # what a library built from an earlier commit (EKF_LIB, the A/B tools) may lack
-LATER_EXPORTS = TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident")
+EVAL_EXPORTS = ("ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval")
+LATER_EXPORTS = TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident") + EVAL_EXPORTS
+EKF_EVAL_POSE_NOT_PD, EKF_EVAL_LM_NOT_PD = 1, 2
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
 
 
@@ -88,6 +91,39 @@ class TraceRec(C.Structure):
 TRACE_DTYPE = np.dtype([("pose", np.float64, 3), ("map_odom", np.float64, 3),
                         ("seq", np.int64), ("reserved", np.int64)])
 assert TRACE_DTYPE.itemsize == C.sizeof(TraceRec) == 64
+
+
+class LmMarginal(C.Structure):
+    """ekf_lm_marginal (include/ekf.h): one landmark slot's estimate and 2 x 2 block, 48 bytes."""
+    _fields_ = [("xy", C.c_double * 2), ("cov", C.c_double * 3), ("seen", C.c_int),
+                ("pad", C.c_int)]
+
+
+class EvalRec(C.Structure):
+    """ekf_eval_rec (include/ekf.h): one filter's score against the truth, 128 bytes."""
+    _fields_ = [("pose_err", C.c_double * 3), ("pose_cov", C.c_double * 6),
+                ("pose_nees", C.c_double), ("lm_sq_err", C.c_double), ("lm_nees", C.c_double),
+                ("lm_max_err", C.c_double), ("lm_var_trace", C.c_double),
+                ("n_seen", C.c_int), ("n_eval", C.c_int), ("n_nees", C.c_int),
+                ("flags", C.c_uint)]
+
+
+class EvalSum(C.Structure):
+    """ekf_eval_sum (include/ekf.h): a swarm's records in a few numbers."""
+    _fields_ = [("n", C.c_int), ("n_pose_nees", C.c_int), ("anees_pose", C.c_double),
+                ("pose_in_95", C.c_double), ("pos_rmse", C.c_double),
+                ("heading_rmse", C.c_double), ("lm_rmse", C.c_double), ("anees_lm", C.c_double)]
+
+
+LM_MARGINAL_DTYPE = np.dtype([("xy", np.float64, 2), ("cov", np.float64, 3), ("seen", np.int32),
+                              ("pad", np.int32)])
+EVAL_DTYPE = np.dtype([("pose_err", np.float64, 3), ("pose_cov", np.float64, 6),
+                       ("pose_nees", np.float64), ("lm_sq_err", np.float64),
+                       ("lm_nees", np.float64), ("lm_max_err", np.float64),
+                       ("lm_var_trace", np.float64), ("n_seen", np.int32), ("n_eval", np.int32),
+                       ("n_nees", np.int32), ("flags", np.uint32)])
+assert LM_MARGINAL_DTYPE.itemsize == C.sizeof(LmMarginal) == 48
+assert EVAL_DTYPE.itemsize == C.sizeof(EvalRec) == 128
 
 
 class Config(C.Structure):
@@ -180,10 +216,15 @@ def lib():
             "ekf_sim_run": (_i, [_vp, _i, _vp, _vp]),
             "ekf_sim_markers": (_i, [_vp, _vp, _vp, _vp, _vp]),
             "ekf_sim_poses": (_i, [_vp, _vp, _vp]),
+            "ekf_get_marginals": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+            "ekf_eval": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+            "ekf_eval_summary": (_i, [_vp, _i, C.POINTER(EvalSum)]),
+            "ekf_sim_eval": (_i, [_vp, _vp]),
         }
         for name, (res, argt) in sig.items():
             # (EKF_LIB naming a library built from an earlier commit, for the A/B tools: it loads
-            # without the pose trace or the resident device replays, and a call of one fails;
+            # without the pose trace, the resident device replays or the scoring, and a call of one
+            # fails;
             # build() checks EXPORTS)
             if name in LATER_EXPORTS and not hasattr(L, name):
                 continue
@@ -459,6 +500,31 @@ class EKF:
     def trace_clear(self, f=-1):
         _check(lib().ekf_trace_clear(self.h, f), "ekf_trace_clear")
 
+    # marginals and scoring (ekf_get_marginals, ekf_eval): gathered on the device, read-only
+    def marginals(self, f=None):
+        """ekf_get_marginals of filter f, or of every filter (f = None: a leading [F] axis):
+        (pose [3], pose_cov [3, 3], lm [N] of LM_MARGINAL_DTYPE, counter). Synchronises."""
+        lead = (self.F,) if f is None else ()
+        pose = np.zeros(lead + (3,))
+        cov = np.zeros(lead + (3, 3))
+        lm = np.zeros(lead + (self.N,), LM_MARGINAL_DTYPE)
+        cnt = np.zeros(lead + (1,), np.uint32)
+        _check(lib().ekf_get_marginals(self.h, -1 if f is None else f, _ptr(pose), _ptr(cov),
+                                       _ptr(lm), _ptr(cnt)), "ekf_get_marginals")
+        return pose, cov, lm, (cnt[..., 0] if f is None else int(cnt[0]))
+
+    def eval(self, truth_pose, truth_lm=None, frame=None):
+        """ekf_eval: every filter against truth_pose [F, 3] and truth_lm [F, n_map, 2] (NaN: no
+        truth for the slot; None: poses only), frame = (theta0, x0, y0) of the map frame in the
+        truth's frame or None. Returns [F] records of EVAL_DTYPE. Synchronises."""
+        tp = _f64(truth_pose).reshape(self.F, 3)
+        tl = None if truth_lm is None else _f64(truth_lm).reshape(self.F, -1, 2)
+        fr = None if frame is None else _f64(frame).reshape(3)
+        out = np.zeros(self.F, EVAL_DTYPE)
+        _check(lib().ekf_eval(self.h, _ptr(tp), _ptr(tl), 0 if tl is None else tl.shape[1],
+                              _ptr(fr), _ptr(out)), "ekf_eval")
+        return out
+
     def status(self, f=0) -> int:
         fl = C.c_uint(0)
         _check(lib().ekf_get_status(self.h, f, C.byref(fl)), "ekf_get_status")
@@ -606,6 +672,13 @@ class Sim:
         _check(lib().ekf_sim_poses(self.h, _ptr(odom), _ptr(truth)), "ekf_sim_poses")
         return odom, truth
 
+    def eval(self):
+        """ekf_sim_eval: every filter against the simulator's device-resident truth (its true
+        poses, its map, frame = the start pose). Returns [F] records of EVAL_DTYPE."""
+        out = np.zeros(self.F, EVAL_DTYPE)
+        _check(lib().ekf_sim_eval(self.h, _ptr(out)), "ekf_sim_eval")
+        return out
+
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             lib().ekf_sim_destroy(self.h)
@@ -616,6 +689,15 @@ class Sim:
             self.close()
         except Exception:
             pass
+
+
+def eval_summary(recs) -> dict:
+    """ekf_eval_summary of [F] records of EVAL_DTYPE (pure host code): a dict of ekf_eval_sum's
+    fields."""
+    recs = np.ascontiguousarray(recs, dtype=EVAL_DTYPE)
+    out = EvalSum()
+    _check(lib().ekf_eval_summary(_ptr(recs), len(recs), C.byref(out)), "ekf_eval_summary")
+    return {name: getattr(out, name) for name, _ in EvalSum._fields_}
 
 
 def poison_lds(device=0):

@@ -333,6 +333,84 @@ int ekf_trace_count(ekf_t h, int filter, long long* appended);
 int ekf_trace_read(ekf_t h, int filter, long long first, int n, ekf_trace_rec* out, int* got);
 int ekf_trace_clear(ekf_t h, int filter); /* filter < 0: every filter */
 
+/* ---- marginals and scoring: the parts of Σ a consumer needs, gathered on the device ---- */
+/* ekf_get_state copies a filter's whole n × ld Σ (2.1 MB at N = 256). What a node draws (the
+ * covariance ellipses that go with green/obstacles) and what a Monte-Carlo run is scored by need
+ * the 3 × 3 pose block and the N diagonal 2 × 2 landmark blocks only: a kernel gathers those from
+ * where they lie and, for a score, reduces them against the truth on the device.
+ *   Every call here synchronises like ekf_get_* (it submits what is planned and waits for both
+ *     streams), runs its kernel on the handle's stream and copies the result back.
+ *   The filter is left alone: Σ, the state, the status flags, the decisions, the pose trace and the
+ *     planning state are only read, so a replay continued after one of these calls gives the bits
+ *     it gives after an ekf_get_pose in its place.
+ *   Blocks are widened to fp64 and symmetrised, ½(Σ[i][j] + Σ[j][i]): fp32 and resident handles keep
+ *     Σ symmetric only up to rounding.
+ *   A landmark slot is `seen` unless both its coordinates are exactly 0, the reference's own
+ *     first-sighting test (slam.cpp:213). */
+typedef struct {
+  double xy[2];  /* state(3 + 2j), state(4 + 2j) */
+  double cov[3]; /* xx, xy, yy of the slot's 2 × 2 block */
+  int seen;
+  int pad;       /* 0 */
+} ekf_lm_marginal; /* 48 bytes */
+
+/* pose[3] = state(0..2); pose_cov[9] row-major (θ, x, y); lm[N]; counter = counter_obstacles. Every
+ * output is nullable. filter < 0: every filter, and each array gets a leading [n_filters] axis.
+ * EKF_E_ARG: a NULL handle, filter >= n_filters. */
+int ekf_get_marginals(ekf_t h, int filter, double* pose, double* pose_cov, ekf_lm_marginal* lm,
+                      unsigned* counter);
+
+#define EKF_EVAL_POSE_NOT_PD 1u /* the pose block is not positive definite: pose_nees is NaN */
+#define EKF_EVAL_LM_NOT_PD 2u   /* an evaluated landmark's block is not positive definite */
+
+/* One filter's score against the truth.
+ *   pose_err      (normalize_angle(θ̂ − θ), x̂ − x, ŷ − y)
+ *   pose_cov      the symmetrised pose block: tt tx ty xx xy yy
+ *   pose_nees     eᵀP⁻¹e by a 3 × 3 Cholesky (square-root free); a pivot <= 0 or not finite gives
+ *                 NaN and EKF_EVAL_POSE_NOT_PD (a fresh filter's pose block is exactly 0)
+ * A landmark slot j is evaluated when it is seen, j < n_map, and its truth is not NaN:
+ *   n_seen, n_eval          seen slots; evaluated slots
+ *   lm_sq_err, lm_max_err   Σ |p̂ − p|² and max |p̂ − p| over the evaluated slots
+ *   lm_nees, n_nees         Σ of the 2 × 2 NEES over the evaluated slots whose block is positive
+ *                           definite, and how many those are; any other evaluated slot sets
+ *                           EKF_EVAL_LM_NOT_PD
+ *   lm_var_trace            Σ of the blocks' traces over the seen slots
+ * The sums are taken in one fixed order: the same state and truth give the same bytes. */
+typedef struct {
+  double pose_err[3];
+  double pose_cov[6];
+  double pose_nees, lm_sq_err, lm_nees, lm_max_err, lm_var_trace;
+  int n_seen, n_eval, n_nees;
+  unsigned flags; /* EKF_EVAL_* */
+} ekf_eval_rec;   /* 128 bytes */
+
+/* Scores every filter of the handle: truth_pose[F][3] (θ, x, y), truth_lm[F][n_map][2] (NULL with
+ * n_map = 0: poses only), out[F]. A NaN coordinate in truth_lm marks "no truth for this slot"; a
+ * caller whose association is unknown permutes its truth into slot order first.
+ * frame[3] = (θ0, x0, y0) (nullable): the map frame's pose in the truth's frame. The truth is
+ * brought into the map frame first, pose (normalize_angle(θ − θ0), R(θ0)ᵀ((x, y) − (x0, y0))) and
+ * landmarks likewise; NULL: no transform at all.
+ * EKF_E_ARG, and nothing is touched: a NULL handle, truth_pose or out; n_map outside [0, N];
+ * truth_lm NULL with n_map > 0. */
+int ekf_eval(ekf_t h, const double* truth_pose, const double* truth_lm, int n_map,
+             const double* frame, ekf_eval_rec* out);
+
+/* A swarm's records in a few numbers. Pure host code: no handle, no GPU. A ratio whose denominator
+ * is zero is NaN. */
+typedef struct {
+  int n;               /* records */
+  int n_pose_nees;     /* finite pose_nees among them */
+  double anees_pose;   /* their mean (3 for a consistent filter) */
+  double pose_in_95;   /* share of them <= 7.814727903251179, χ²₃ at 0.95 */
+  double pos_rmse;     /* √mean(ex² + ey²) */
+  double heading_rmse; /* √mean(eθ²) */
+  double lm_rmse;      /* √(Σ lm_sq_err / Σ n_eval) */
+  double anees_lm;     /* Σ lm_nees / Σ n_nees (2 for a consistent filter) */
+} ekf_eval_sum;
+
+/* EKF_E_ARG: recs or out NULL, nf < 1. */
+int ekf_eval_summary(const ekf_eval_rec* recs, int nf, ekf_eval_sum* out);
+
 /* ---- helpers ---- */
 /* turtlelib::normalize_angle (geometry2d.cpp:5-14): maps into (-π, π], -π → π. */
 double ekf_normalize_angle(double rad);

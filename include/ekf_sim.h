@@ -22,6 +22,8 @@
  * message's descriptor itself, so a swarm replay is a few launches per upload window.
  * The same arithmetic, draw for draw, is restated on the host by pyekf.synth (the test oracle of
  * this path); the filter then equals oracle/ runs fed the device's own markers.
+ * The last stage of a Monte-Carlo run, scoring the estimate against this truth (pose and map error,
+ * NEES), runs on the device too: ekf_sim_eval.
  *
  * Collisions with obstacles (nusim.cpp:232-254) are not modelled: landmarks are placed clear of
  * the path. Unknown association (ids stripped) is not supported here (ekf_replay is). */
@@ -78,6 +80,14 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense);
  * truth[T][F][3] (θ, x, y). Synchronises. */
 int ekf_sim_markers(ekf_sim_t s, int* counts, int* ids, int* actions, double* rel_xy);
 int ekf_sim_poses(ekf_sim_t s, double* odom, double* truth);
+
+/* Scores every filter of the handle against the simulator's own truth (ekf_eval, ekf.h): each
+ * filter's true pose after the last simulated tick and its map landmarks[F][L][2], both where the
+ * simulator keeps them on the device, with frame = (start_theta, start_x, start_y) — the filter
+ * starts at 0 where the truth starts at the configured pose. The truth never visits the host; only
+ * out[F] comes back. Needs no cfg.record. Synchronises; the filter is left alone as by ekf_eval.
+ * EKF_E_ARG: a NULL simulator or out. */
+int ekf_sim_eval(ekf_sim_t s, ekf_eval_rec* out);
 
 #ifdef __cplusplus
 }
