@@ -9,6 +9,7 @@
 #include "ekf_ctx.hpp"
 #include "ekf_internal.hpp"
 #include "geom.hpp"
+#include "match_math.hpp"
 
 using namespace ekfslam;
 
@@ -31,6 +32,27 @@ int load_and_plan(ekf_ctx* h, int assoc_mode, int m_max, const int* counts, cons
 // ---- gather and score (ekf_eval.hip): one device buffer per call, carved 16 bytes at a time ----
 
 size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
+
+// A scoring launch with start / stop events on its dispatch when profiling (ekf_profile_read).
+template <typename Fn>
+hipError_t timed_eval(ekf_ctx* h, ProfSlot kind, Fn fn) {
+  auto take = [&]() -> hipEvent_t {
+    hipEvent_t e = nullptr;
+    if (!h->pool.empty()) {
+      e = h->pool.back();
+      h->pool.pop_back();
+    } else if (hipEventCreate(&e) != hipSuccess) {
+      e = nullptr;
+    }
+    return e;
+  };
+  hipEvent_t a = h->prof ? take() : nullptr, b = h->prof ? take() : nullptr;
+  if (!a || !b) return fn(nullptr, nullptr);
+  const hipError_t e = fn(a, b);
+  h->pe[kind].start.push_back(a);
+  h->pe[kind].stop.push_back(b);
+  return e;
+}
 
 int eval_reserve(ekf_ctx* h, size_t bytes) {
   if (bytes <= h->eval_cap) return EKF_OK;
@@ -102,8 +124,10 @@ int eval_run(ekf_ctx* h, const double* h_pose, const double* h_lm, const double*
   for (int k = 0; k < 3; ++k) t.frame[k] = frame ? frame[k] : 0.0;
   EvalArgs a;
   if (int rc = eval_args(h, par, 0, &a)) return rc;
-  HIPCHK(by_dtype(h, [&](auto tag) {
-    return launch_eval<decltype(tag)>(a, t, rec, h->F, h->stream);
+  HIPCHK(timed_eval(h, kProfEval, [&](hipEvent_t e0, hipEvent_t e1) {
+    return by_dtype(h, [&](auto tag) {
+      return launch_eval<decltype(tag)>(a, t, rec, h->F, h->stream, e0, e1);
+    });
   }));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(out, rec, rec_b, hipMemcpyDeviceToHost));
@@ -114,7 +138,70 @@ bool eval_args_ok(const ekf_ctx* h, const void* pose, const void* lm, int n_map,
   return h && pose && out && n_map >= 0 && n_map <= h->cfg.n_landmarks && (lm || n_map == 0);
 }
 
+// ekf_eval_match: the truth as eval_run takes it (from the host, or with h_pose NULL on the
+// device), in any order. Arguments checked by the callers.
+int eval_match_run(ekf_ctx* h, const double* h_pose, const double* h_lm, const double* d_pose,
+                   size_t pose_stride, const double* d_lm, int n_map, const double* frame,
+                   double max_dist, ekf_eval_rec* out, ekf_match_rec* match_out, int* match) {
+  if (int rc = settle(h)) return rc;
+  hipSetDevice(h->cfg.device);
+  const size_t F = static_cast<size_t>(h->F), N = static_cast<size_t>(h->cfg.n_landmarks);
+  const size_t par_b = up16(F * sizeof(int)), rec_b = F * sizeof(EvalRec),
+               mrec_b = F * sizeof(MatchRec), match_b = up16(F * N * sizeof(int));
+  const size_t pose_b = h_pose ? up16(F * 3 * sizeof(double)) : 0;
+  const size_t lm_b = h_pose ? up16(F * n_map * 2 * sizeof(double)) : 0;
+  if (int rc = eval_reserve(h, par_b + rec_b + mrec_b + match_b + pose_b + lm_b)) return rc;
+  char* base = static_cast<char*>(h->eval_buf);
+  MatchOut o{};
+  o.rec = reinterpret_cast<EvalRec*>(base + par_b);
+  o.mrec = reinterpret_cast<MatchRec*>(base + par_b + rec_b);
+  o.match = reinterpret_cast<int*>(base + par_b + rec_b + mrec_b);
+  if (h_pose) {
+    double* up = reinterpret_cast<double*>(base + par_b + rec_b + mrec_b + match_b);
+    double* ul = reinterpret_cast<double*>(base + par_b + rec_b + mrec_b + match_b + pose_b);
+    HIPCHK(hipMemcpy(up, h_pose, F * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ul, h_lm, F * n_map * 2 * sizeof(double), hipMemcpyHostToDevice));
+    d_pose = up;
+    pose_stride = 3;
+    d_lm = ul;
+  }
+  EvalTruth t{};
+  t.pose = d_pose;
+  t.pose_stride = pose_stride;
+  t.lm = d_lm;
+  t.n_map = n_map;
+  t.has_frame = frame != nullptr;
+  for (int k = 0; k < 3; ++k) t.frame[k] = frame ? frame[k] : 0.0;
+  EvalArgs a;
+  if (int rc = eval_args(h, reinterpret_cast<int*>(base), 0, &a)) return rc;
+  const double gate2 = max_dist * max_dist;
+  HIPCHK(timed_eval(h, kProfEvalMatch, [&](hipEvent_t e0, hipEvent_t e1) {
+    return by_dtype(h, [&](auto tag) {
+      return launch_eval_match<decltype(tag)>(a, t, gate2, o, h->F, h->stream, e0, e1);
+    });
+  }));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(out, o.rec, rec_b, hipMemcpyDeviceToHost));
+  if (match_out) HIPCHK(hipMemcpy(match_out, o.mrec, mrec_b, hipMemcpyDeviceToHost));
+  if (match) HIPCHK(hipMemcpy(match, o.match, F * N * sizeof(int), hipMemcpyDeviceToHost));
+  return EKF_OK;
+}
+
+// (max_dist: not negative and not NaN; +∞ is valid)
+bool match_args_ok(const ekf_ctx* h, const void* pose, const void* lm, int n_map, double max_dist,
+                   const void* out) {
+  return h && pose && lm && out && n_map >= 1 && n_map <= kMatchMaxMap && max_dist >= 0.0;
+}
+
 }  // namespace
+
+int ekfslam::eval_match_device(ekf_t h, const double* d_pose, size_t pose_stride,
+                               const double* d_lm, int n_map, const double* frame, double max_dist,
+                               ekf_eval_rec* out, ekf_match_rec* match_out, int* match) {
+  if (!match_args_ok(h, d_pose, d_lm, n_map, max_dist, out)) return EKF_E_ARG;
+  return eval_match_run(h, nullptr, nullptr, d_pose, pose_stride, d_lm, n_map, frame, max_dist, out,
+                        match_out, match);
+}
 
 int ekfslam::eval_device(ekf_t h, const double* d_pose, size_t pose_stride, const double* d_lm,
                          int n_map, const double* frame, ekf_eval_rec* out) {
@@ -744,6 +831,14 @@ int ekf_eval(ekf_t h, const double* truth_pose, const double* truth_lm, int n_ma
              const double* frame, ekf_eval_rec* out) {
   if (!eval_args_ok(h, truth_pose, truth_lm, n_map, out)) return EKF_E_ARG;
   return eval_run(h, truth_pose, truth_lm, nullptr, 0, nullptr, n_map, frame, out);
+}
+
+int ekf_eval_match(ekf_t h, const double* truth_pose, const double* truth_lm, int n_map,
+                   const double* frame, double max_dist, ekf_eval_rec* out,
+                   ekf_match_rec* match_out, int* match) {
+  if (!match_args_ok(h, truth_pose, truth_lm, n_map, max_dist, out)) return EKF_E_ARG;
+  return eval_match_run(h, truth_pose, truth_lm, nullptr, 0, nullptr, n_map, frame, max_dist, out,
+                        match_out, match);
 }
 
 int ekf_eval_summary(const ekf_eval_rec* recs, int nf, ekf_eval_sum* out) {

@@ -35,7 +35,9 @@ enum ProfSlot : int {
   kProfAssoc = 2,     // association
   kProfFactors = 3,   // factors
   kProfResident = 4,  // resident filter kernel
-  kProfSlots = 5,
+  kProfEval = 5,      // k_eval (ekf_eval, ekf_sim_eval)
+  kProfEvalMatch = 6, // k_eval_match (ekf_eval_match, ekf_sim_eval_match)
+  kProfSlots = 7,
 };
 
 }  // namespace ekfslam

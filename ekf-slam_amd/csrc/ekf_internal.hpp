@@ -14,6 +14,7 @@ struct HandleInfo {
   int F, N, n, dtype, device;
   bool resident;  // n ≤ kResidentMaxN fp64: one resident launch per plan
   bool joseph;    // ekf_set_joseph is on (the HBM pipeline then needs one marker per chunk)
+  bool serial;    // EKF_SCHED_SERIAL: every kernel runs on `stream`
   hipStream_t stream;
   hipStream_t bulk;  // the factors / Σ-pass stream (the main stream when serial)
 };
@@ -51,5 +52,10 @@ int replay_markers_resident(ekf_t h, int device, int T, int m_max, const int* d_
 // Synchronises like ekf_get_*; out[F] on the host. EKF_E_ARG as ekf_eval's.
 int eval_device(ekf_t h, const double* d_pose, size_t pose_stride, const double* d_lm, int n_map,
                 const double* frame, ekf_eval_rec* out);
+// ekf_eval_match likewise (ekf_sim_eval_match): d_lm[F][n_map][2] in any order. EKF_E_ARG as
+// ekf_eval_match's.
+int eval_match_device(ekf_t h, const double* d_pose, size_t pose_stride, const double* d_lm,
+                      int n_map, const double* frame, double max_dist, ekf_eval_rec* out,
+                      ekf_match_rec* match_out, int* match);
 
 }  // namespace ekfslam

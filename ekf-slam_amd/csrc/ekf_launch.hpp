@@ -236,7 +236,20 @@ template <typename T>
 hipError_t launch_marginals(const EvalArgs& a, const MarginalOut& o, int n_filters, hipStream_t s);
 template <typename T>
 hipError_t launch_eval(const EvalArgs& a, const EvalTruth& t, EvalRec* out, int n_filters,
-                       hipStream_t s);
+                       hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// (e0, e1: start / stop events carried by the dispatch when both are given, ekf_profile_read)
+// ekf_eval_match: t.lm is the truth map in any order, 1 ≤ t.n_map ≤ 1024 (staged in LDS; anything
+// else is refused with hipErrorInvalidValue); gate2 = max_dist². Every output is required.
+struct MatchRec;  // match_math.hpp
+struct MatchOut {
+  EvalRec* rec;    // [n_filters]
+  MatchRec* mrec;  // [n_filters]
+  int* match;      // [n_filters][N]: the slot's truth landmark, −1 unseen or unmatched
+};
+template <typename T>
+hipError_t launch_eval_match(const EvalArgs& a, const EvalTruth& t, double gate2, const MatchOut& o,
+                             int n_filters, hipStream_t s, hipEvent_t e0 = nullptr,
+                             hipEvent_t e1 = nullptr);
 
 // Σ₀ diagonal: Σ[i][i] = v for i ≥ 3 (the rest is zero-filled by the caller).
 template <typename T>

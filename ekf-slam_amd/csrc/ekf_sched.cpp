@@ -866,6 +866,7 @@ int handle_info(ekf_t h, HandleInfo* out) {
   out->device = h->cfg.device;
   out->resident = h->resident;
   out->joseph = h->plan.joseph();
+  out->serial = h->serial;
   out->stream = h->stream;
   out->bulk = h->bulk ? h->bulk : h->stream;
   return EKF_OK;

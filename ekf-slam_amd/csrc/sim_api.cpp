@@ -6,6 +6,8 @@
 // A run without SURVEY messages on the HBM pipeline takes the parallel form instead: the wheels per
 // filter, then every (message, filter) sensed at once into marker arrays, which ekf_replay_device
 // plans on the GPU — no host round trip at all (EKF_SIM_PARALLEL=0 keeps the sequential kernel).
+// ekf_sim_run_assoc always simulates in the parallel form and hands the marker arrays, ids ignored,
+// to the device-input association replay of the handle's path.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +57,8 @@ struct ekf_sim {
     double* odomF = nullptr;  // [T][F][3] (the planner's input)
   } mk[2];
   bool mk_alloc = false;
+  int mk_bufs = 0;                  // marker buffers allocated (reserve)
+  bool assoc = false;               // ekf_sim_run_assoc has been called: both marker buffers, always
   int last_T = 0, last_b = 0;
   std::vector<int> host_par;
   std::vector<double> host_odom;    // [F][3] t_odom_robot after the last run
@@ -82,6 +86,7 @@ void free_run(ekf_sim* s) {
   }
   s->plan = nullptr;
   s->mk_alloc = false;
+  s->mk_bufs = 0;
   s->cap_ticks = s->cap_msgs = 0;
 }
 
@@ -98,22 +103,27 @@ bool parallel_ok(const ekf_sim* s, int T, const int* sense) {
 int reserve(ekf_sim* s, int T) {
   const size_t F = static_cast<size_t>(s->info.F), M = static_cast<size_t>(s->cfg.marker_stride);
   const size_t ticks = static_cast<size_t>(T) * s->cfg.ticks_per_msg;
-  if (static_cast<size_t>(T) <= s->cap_msgs && ticks <= s->cap_ticks) return EKF_OK;
+  // markers: both buffers for the parallel form (one run's planner reads them while the next run's
+  // simulation writes the other) and, at any stride and on either path, once ekf_sim_run_assoc has
+  // been called (its replays read them); buffer 0 only for a record of the sequential form
+  const bool par = !s->info.resident && s->cfg.marker_stride <= kMaxChunk;
+  const int bufs = par || s->assoc ? 2 : s->cfg.record ? 1 : 0;
+  if (static_cast<size_t>(T) <= s->cap_msgs && ticks <= s->cap_ticks && bufs <= s->mk_bufs)
+    return EKF_OK;
+  // (the bulk stream too: an association replay of ekf_sim_run_assoc may still read the buffers)
   if (hipStreamSynchronize(s->info.stream) != hipSuccess ||
+      hipStreamSynchronize(s->info.bulk) != hipSuccess ||
       hipStreamSynchronize(s->sst) != hipSuccess)
     return EKF_E_HIP;
+  const size_t Tn = std::max<size_t>({static_cast<size_t>(T), s->cap_msgs, 1});
   free_run(s);
-  const size_t Tn = std::max<size_t>(T, 1);
   const size_t tk = Tn * s->cfg.ticks_per_msg;
   bool ok = hipMalloc(&s->plan, Tn * sizeof(PlanEntry)) == hipSuccess;
   for (int b = 0; b < 2 && ok; ++b)
     ok = hipMalloc(&s->cmd[b], tk * 2 * sizeof(double)) == hipSuccess &&
          hipMalloc(&s->sense[b], Tn * sizeof(int)) == hipSuccess &&
          hipMalloc(&s->desc[b], Tn * F * sizeof(MsgDesc)) == hipSuccess;
-  // markers: both buffers for the parallel form (one run's planner reads them while the next run's
-  // simulation writes the other), buffer 0 only for a record of the sequential form
-  const bool par = !s->info.resident && s->cfg.marker_stride <= kMaxChunk;
-  for (int b = 0; b < (par ? 2 : 1) && ok && (par || s->cfg.record); ++b) {
+  for (int b = 0; b < bufs && ok; ++b) {
     auto& k = s->mk[b];
     ok = hipMalloc(&k.ids, Tn * F * M * sizeof(int)) == hipSuccess &&
          hipMalloc(&k.act, Tn * F * M * sizeof(int)) == hipSuccess &&
@@ -137,15 +147,13 @@ int reserve(ekf_sim* s, int T) {
   }
   s->cap_msgs = Tn;
   s->cap_ticks = tk;
+  s->mk_bufs = bufs;
   return EKF_OK;
 }
 
-// The parallel form of ekf_sim_run (parallel_ok): simulation on the simulator's stream, then
-// ekf_replay_device over its marker arrays behind it on the handle's streams. The planning state
-// stays on the device (the handle adopts it at its next host access), so the host never waits.
-int run_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sense) {
-  const int b = s->buf;
-  s->buf ^= 1;
+// The simulation of the parallel form into run buffer b, on the simulator's stream; the handle's
+// streams wait for it. Advances the tick and message counters.
+int simulate_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sense, int b) {
   const hipStream_t st = s->sst;
   const size_t ticks = static_cast<size_t>(T) * s->cfg.ticks_per_msg;
   auto& k = s->mk[b];
@@ -192,11 +200,42 @@ int run_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sense) {
   s->msg += T;
   s->last_T = T;
   s->last_b = b;
+  return EKF_OK;
+}
+
+// The parallel form of ekf_sim_run (parallel_ok): simulation on the simulator's stream, then
+// ekf_replay_device over its marker arrays behind it on the handle's streams. The planning state
+// stays on the device (the handle adopts it at its next host access), so the host never waits.
+int run_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sense) {
+  const int b = s->buf;
+  s->buf ^= 1;
+  if (int rc = simulate_parallel(s, T, wheel_cmd, sense, b)) return rc;
+  const auto& k = s->mk[b];
   const int rc = ekf_replay_device(s->h, T, s->cfg.marker_stride, k.cnt, k.ids, k.act, k.rel,
                                    k.odomF);
   if (rc) return rc;
   // the chain launch on the main stream polls the planner (or follows it): done there ⇒ read
   return hipEventRecord(s->ev_done[b], s->info.stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+}
+
+// ekf_sim_run_assoc: the same simulation, handed over with the ids ignored. Which stream reads the
+// buffers (ekf_sched.cpp): replay_device_assoc puts its planner k_plan_assoc, the only reader, and
+// every association launch behind it on the main stream of a serial handle and on the bulk stream
+// otherwise (`ps`); replay_resident launches k_resident_replay, which reads them throughout, on the
+// main stream, the only one a resident handle uses. ev_done[b] is recorded on that stream behind
+// the replay's last launch, so the run after next rewrites buffer b only once all of it has ended.
+int run_assoc(ekf_sim* s, int T, const double* wheel_cmd) {
+  const int b = s->buf;
+  s->buf ^= 1;
+  if (int rc = simulate_parallel(s, T, wheel_cmd, nullptr, b)) return rc;
+  const auto& k = s->mk[b];
+  const int M = s->cfg.marker_stride;
+  const int rc = s->info.resident
+                     ? ekf_replay_resident(s->h, 1, T, M, k.cnt, nullptr, nullptr, k.rel, 2, k.odomF)
+                     : ekf_replay_device_assoc(s->h, T, M, k.cnt, k.rel, 2, k.odomF);
+  if (rc) return rc;
+  const hipStream_t rs = s->info.resident || s->info.serial ? s->info.stream : s->info.bulk;
+  return hipEventRecord(s->ev_done[b], rs) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 }  // namespace
@@ -319,6 +358,9 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense) {
     return EKF_E_HIP;
   // buffer b was last read by the filter work of the run before the previous one
   if (hipStreamWaitEvent(st, s->ev_done[b], 0) != hipSuccess) return EKF_E_HIP;
+  // (the record goes into marker buffer 0 whatever b is: a replay of the run before may read it)
+  if (s->cfg.record && b != 0 && hipStreamWaitEvent(st, s->ev_done[0], 0) != hipSuccess)
+    return EKF_E_HIP;
   if (hipMemcpyAsync(s->cmd[b], wheel_cmd, ticks * 2 * sizeof(double), hipMemcpyHostToDevice, st) !=
       hipSuccess)
     return EKF_E_HIP;
@@ -383,6 +425,21 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense) {
   return hipEventRecord(s->ev_done[b], s->info.stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
+int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd) {
+  if (!s || T < 0 || (T > 0 && !wheel_cmd) || s->cfg.marker_stride > kMaxAssoc) return EKF_E_ARG;
+  // what the replay underneath would refuse, before the simulator moves: a pipeline handle on the
+  // one-marker route has no device-planned association replay
+  int route = EKF_ASSOC_MARKER;
+  if (int rc = ekf_get_assoc_route(s->h, &route)) return rc;
+  if (!s->info.resident && route == EKF_ASSOC_MARKER) return EKF_E_ARG;
+  if (T == 0) return EKF_OK;
+  if (int rc = handle_info(s->h, &s->info)) return rc;  // host-planned work first, bulk joined
+  hipSetDevice(s->info.device);
+  s->assoc = true;
+  if (int rc = reserve(s, T)) return rc;
+  return run_assoc(s, T, wheel_cmd);
+}
+
 int ekf_sim_markers(ekf_sim_t s, int* counts, int* ids, int* actions, double* rel_xy) {
   if (!s || !s->cfg.record) return EKF_E_ARG;
   const size_t n = static_cast<size_t>(s->last_T) * s->info.F, M = s->cfg.marker_stride;
@@ -420,6 +477,16 @@ int ekf_sim_eval(ekf_sim_t s, ekf_eval_rec* out) {
   const double frame[3] = {s->cfg.start_theta, s->cfg.start_x, s->cfg.start_y};
   return eval_device(s->h, s->st->truth, sizeof(SimState) / sizeof(double), s->lm, s->L, frame,
                      out);
+}
+
+int ekf_sim_eval_match(ekf_sim_t s, double max_dist, ekf_eval_rec* out, ekf_match_rec* match_out,
+                       int* match) {
+  if (!s || !out || !(max_dist >= 0.0)) return EKF_E_ARG;
+  hipSetDevice(s->info.device);
+  if (hipStreamSynchronize(s->sst) != hipSuccess) return EKF_E_HIP;  // (as ekf_sim_eval)
+  const double frame[3] = {s->cfg.start_theta, s->cfg.start_x, s->cfg.start_y};
+  return eval_match_device(s->h, s->st->truth, sizeof(SimState) / sizeof(double), s->lm, s->L,
+                           frame, max_dist, out, match_out, match);
 }
 
 }  // extern "C"

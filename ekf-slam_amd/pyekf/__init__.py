@@ -50,12 +50,16 @@ EXPORTS = [
     "ekf_sim_config_default", "ekf_sim_create", "ekf_sim_destroy", "ekf_sim_run",
     "ekf_sim_markers", "ekf_sim_poses",
     "ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval",
+    "ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match",
 ]
 TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear",
                  "slam_replay_trace")
 # what a library built from an earlier commit (EKF_LIB, the A/B tools) may lack
 EVAL_EXPORTS = ("ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval")
-LATER_EXPORTS = TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident") + EVAL_EXPORTS
+MATCH_EXPORTS = ("ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match")
+LATER_EXPORTS = (TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident") + EVAL_EXPORTS +
+                 MATCH_EXPORTS)
+EKF_MATCH_MAX_MAP = 1024
 EKF_EVAL_POSE_NOT_PD, EKF_EVAL_LM_NOT_PD = 1, 2
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
 
@@ -108,6 +112,13 @@ class EvalRec(C.Structure):
                 ("flags", C.c_uint)]
 
 
+class MatchRec(C.Structure):
+    """ekf_match_rec (include/ekf.h): one filter's association quality, 32 bytes."""
+    _fields_ = [("n_truth", C.c_int), ("n_matched", C.c_int), ("n_primary", C.c_int),
+                ("n_dup", C.c_int), ("n_spurious", C.c_int), ("n_missed", C.c_int),
+                ("max_match_dist", C.c_double)]
+
+
 class EvalSum(C.Structure):
     """ekf_eval_sum (include/ekf.h): a swarm's records in a few numbers."""
     _fields_ = [("n", C.c_int), ("n_pose_nees", C.c_int), ("anees_pose", C.c_double),
@@ -124,6 +135,10 @@ EVAL_DTYPE = np.dtype([("pose_err", np.float64, 3), ("pose_cov", np.float64, 6),
                        ("n_nees", np.int32), ("flags", np.uint32)])
 assert LM_MARGINAL_DTYPE.itemsize == C.sizeof(LmMarginal) == 48
 assert EVAL_DTYPE.itemsize == C.sizeof(EvalRec) == 128
+MATCH_DTYPE = np.dtype([("n_truth", np.int32), ("n_matched", np.int32), ("n_primary", np.int32),
+                        ("n_dup", np.int32), ("n_spurious", np.int32), ("n_missed", np.int32),
+                        ("max_match_dist", np.float64)])
+assert MATCH_DTYPE.itemsize == C.sizeof(MatchRec) == 32
 
 
 class Config(C.Structure):
@@ -220,11 +235,14 @@ def lib():
             "ekf_eval": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
             "ekf_eval_summary": (_i, [_vp, _i, C.POINTER(EvalSum)]),
             "ekf_sim_eval": (_i, [_vp, _vp]),
+            "ekf_eval_match": (_i, [_vp, _vp, _vp, _i, _vp, _d, _vp, _vp, _vp]),
+            "ekf_sim_run_assoc": (_i, [_vp, _i, _vp]),
+            "ekf_sim_eval_match": (_i, [_vp, _d, _vp, _vp, _vp]),
         }
         for name, (res, argt) in sig.items():
             # (EKF_LIB naming a library built from an earlier commit, for the A/B tools: it loads
-            # without the pose trace, the resident device replays or the scoring, and a call of one
-            # fails;
+            # without the pose trace, the resident device replays, the scoring or the matching, and a
+            # call of one fails;
             # build() checks EXPORTS)
             if name in LATER_EXPORTS and not hasattr(L, name):
                 continue
@@ -525,6 +543,23 @@ class EKF:
                               _ptr(fr), _ptr(out)), "ekf_eval")
         return out
 
+    def eval_match(self, truth_pose, truth_lm, max_dist, frame=None):
+        """ekf_eval_match: every filter against truth_pose [F, 3] and a truth map in any order,
+        truth_lm [F, n_map, 2] (NaN: no such landmark; n_map <= EKF_MATCH_MAX_MAP): each seen slot
+        is matched to its nearest truth landmark within max_dist and scored against it. Returns
+        (recs [F] of EVAL_DTYPE, match_recs [F] of MATCH_DTYPE, match [F, N] int32: the slot's
+        truth landmark, -1 unseen or unmatched). Synchronises."""
+        tp = _f64(truth_pose).reshape(self.F, 3)
+        tl = _f64(truth_lm).reshape(self.F, -1, 2)
+        fr = None if frame is None else _f64(frame).reshape(3)
+        out = np.zeros(self.F, EVAL_DTYPE)
+        mrec = np.zeros(self.F, MATCH_DTYPE)
+        match = np.full((self.F, self.N), -1, np.int32)
+        _check(lib().ekf_eval_match(self.h, _ptr(tp), _ptr(tl), tl.shape[1], _ptr(fr),
+                                    float(max_dist), _ptr(out), _ptr(mrec), _ptr(match)),
+               "ekf_eval_match")
+        return out, mrec, match
+
     def status(self, f=0) -> int:
         fl = C.c_uint(0)
         _check(lib().ekf_get_status(self.h, f, C.byref(fl)), "ekf_get_status")
@@ -637,6 +672,7 @@ class Sim:
             setattr(c, k, v)
         self.cfg = c
         self.F = ekf.F
+        self.N = ekf.N
         lm = _f64(np.broadcast_to(np.asarray(landmarks, np.float64),
                                   (ekf.F,) + np.shape(landmarks)[-2:]))
         self.L = lm.shape[1]
@@ -651,6 +687,14 @@ class Sim:
         T = cmd.shape[0] // self.cfg.ticks_per_msg
         sn = None if sense is None else _i32(sense)
         _check(lib().ekf_sim_run(self.h, T, _ptr(cmd), _ptr(sn)), "ekf_sim_run")
+        self.T = T
+
+    def run_assoc(self, wheel_cmd):
+        """ekf_sim_run_assoc: the same simulation (every message senses NEAREST), fed to the filter
+        with the ids ignored (unknown association). wheel_cmd[T·ticks][2]."""
+        cmd = _f64(wheel_cmd).reshape(-1, 2)
+        T = cmd.shape[0] // self.cfg.ticks_per_msg
+        _check(lib().ekf_sim_run_assoc(self.h, T, _ptr(cmd)), "ekf_sim_run_assoc")
         self.T = T
 
     def markers(self):
@@ -678,6 +722,16 @@ class Sim:
         out = np.zeros(self.F, EVAL_DTYPE)
         _check(lib().ekf_sim_eval(self.h, _ptr(out)), "ekf_sim_eval")
         return out
+
+    def eval_match(self, max_dist):
+        """ekf_sim_eval_match: EKF.eval_match fed the simulator's device-resident truth (its true
+        poses, its map in any order, frame = the start pose). Returns (recs, match_recs, match)."""
+        out = np.zeros(self.F, EVAL_DTYPE)
+        mrec = np.zeros(self.F, MATCH_DTYPE)
+        match = np.full((self.F, self.N), -1, np.int32)
+        _check(lib().ekf_sim_eval_match(self.h, float(max_dist), _ptr(out), _ptr(mrec),
+                                        _ptr(match)), "ekf_sim_eval_match")
+        return out, mrec, match
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

@@ -386,7 +386,7 @@ typedef struct {
 
 /* Scores every filter of the handle: truth_pose[F][3] (θ, x, y), truth_lm[F][n_map][2] (NULL with
  * n_map = 0: poses only), out[F]. A NaN coordinate in truth_lm marks "no truth for this slot"; a
- * caller whose association is unknown permutes its truth into slot order first.
+ * caller whose association is unknown takes ekf_eval_match below, which finds the slot order itself.
  * frame[3] = (θ0, x0, y0) (nullable): the map frame's pose in the truth's frame. The truth is
  * brought into the map frame first, pose (normalize_angle(θ − θ0), R(θ0)ᵀ((x, y) − (x0, y0))) and
  * landmarks likewise; NULL: no transform at all.
@@ -394,6 +394,44 @@ typedef struct {
  * truth_lm NULL with n_map > 0. */
 int ekf_eval(ekf_t h, const double* truth_pose, const double* truth_lm, int n_map,
              const double* frame, ekf_eval_rec* out);
+
+/* ---- scoring with unknown association: the truth in any order ---- */
+/* After an unknown-association run, slot j holds whatever landmark the filter opened j-th, so there
+ * is no slot order to permute the truth into. ekf_eval_match finds it on the device, in the launch
+ * that scores, and reports the quality of the association itself. Per filter:
+ *   truth_lm[F][n_map][2], 1 <= n_map <= EKF_MATCH_MAX_MAP whatever N is, in any order; a NaN
+ *     coordinate means "no such landmark". The truth is brought into the map frame once, exactly as
+ *     ekf_eval does it.
+ *   k(j), for every seen slot j: the truth landmark with the smallest dx*dx + dy*dy (each product
+ *     rounded on its own), ties to the lowest k (a strict < scan in ascending k). A NaN truth never
+ *     wins, nor does one at an infinite distance.
+ *   Slot j is matched iff that minimum is <= max_dist*max_dist. match[f][j] = k(j) then, and -1 for
+ *     an unseen or unmatched slot.
+ *   Truth k is claimed by the lowest-index slot matched to it: slots open in ascending order, so
+ *     that slot is the landmark's original (its primary) and the others are its duplicates.
+ *   out[f] is the record ekf_eval gives for the same truth_pose and frame with
+ *     truth_perm[j] = truth_lm[match[j]] (NaN where match[j] < 0) and n_map = N, byte for byte: every
+ *     matched slot is evaluated, duplicates included, the terms and the order of the sums are the
+ *     same.
+ * The record holds integers and a maximum: the same state and truth give the same bytes.
+ * EKF_E_ARG, and nothing is touched: a NULL handle, truth_pose, truth_lm or out; n_map outside
+ * [1, EKF_MATCH_MAX_MAP]; max_dist negative or NaN (+infinity is valid). match_out[F] and
+ * match[F][N] are nullable. Synchronises and leaves the filter alone, exactly as ekf_eval does. */
+#define EKF_MATCH_MAX_MAP 1024
+typedef struct {
+  int n_truth;      /* truth landmarks with both coordinates not NaN */
+  int n_matched;    /* seen slots with a truth landmark within max_dist */
+  int n_primary;    /* distinct truth landmarks matched (= matched slots that are the lowest-index
+                       slot of their landmark) */
+  int n_dup;        /* n_matched - n_primary */
+  int n_spurious;   /* n_seen - n_matched */
+  int n_missed;     /* n_truth - n_primary */
+  double max_match_dist; /* largest slot-to-matched-truth distance, 0 if none */
+} ekf_match_rec;    /* 32 bytes */
+
+int ekf_eval_match(ekf_t h, const double* truth_pose, const double* truth_lm, int n_map,
+                   const double* frame, double max_dist, ekf_eval_rec* out,
+                   ekf_match_rec* match_out, int* match);
 
 /* A swarm's records in a few numbers. Pure host code: no handle, no GPU. A ratio whose denominator
  * is zero is NaN. */
@@ -417,7 +455,7 @@ double ekf_normalize_angle(double rad);
 
 /* ---- measurement ---- */
 /* Per-kernel device time (0 = Σ pass, 1 = chain, 2 = association, 3 = factors, 4 = resident filter
- * kernel) from HIP events
+ * kernel, 5 = the scoring kernel of ekf_eval, 6 = that of ekf_eval_match) from HIP events
  * carried by each timed dispatch (hipExtLaunchKernelGGL start/stop events: the kernel's own
  * execution, on the stream it runs on). Off by default. */
 int ekf_profile_enable(ekf_t h, int enable);

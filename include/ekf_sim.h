@@ -24,9 +24,14 @@
  * this path); the filter then equals oracle/ runs fed the device's own markers.
  * The last stage of a Monte-Carlo run, scoring the estimate against this truth (pose and map error,
  * NEES), runs on the device too: ekf_sim_eval.
+ * Unknown association, what the real robot runs (Slam::sensor_cb, slam.cpp:318-530: Mahalanobis
+ * nearest-neighbour association, no ids), has the same two stages: ekf_sim_run_assoc simulates the
+ * same markers and hands them to the filter with the ids ignored, and ekf_sim_eval_match matches the
+ * slots the filter opened to the simulator's map on the device, scores them and reports the
+ * association's quality (duplicate, spurious and missed landmarks).
  *
  * Collisions with obstacles (nusim.cpp:232-254) are not modelled: landmarks are placed clear of
- * the path. Unknown association (ids stripped) is not supported here (ekf_replay is). */
+ * the path. */
 #ifndef EKF_SIM_H
 #define EKF_SIM_H
 
@@ -75,6 +80,22 @@ int ekf_sim_destroy(ekf_sim_t s);
  * With ekf_set_joseph on, the chunks are Joseph-form ones. */
 int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense);
 
+/* T messages with unknown association: simulated exactly as by ekf_sim_run with sense = NULL (every
+ * message senses NEAREST, so every marker is ADD: sensor_cb has no DELETE test, which is why SURVEY
+ * and ALL are not offered here), the same draws and the same bits, always in the parallel form
+ * (EKF_SIM_PARALLEL does not apply). The marker arrays then go to the filter with the ids ignored:
+ * a pipeline handle gets ekf_replay_device_assoc(h, T, marker_stride, counts, rel_xy, 2, odom), a
+ * resident handle ekf_replay_resident(h, 1, T, marker_stride, counts, NULL, NULL, rel_xy, 2, odom).
+ * Nothing crosses PCIe but the wheel commands; asynchronous (the host waits for nothing). The
+ * handle afterwards, its t_odom_robot included, the pose trace, ekf_get_decisions (the last
+ * message's), ekf_set_joseph, ekf_sim_markers and ekf_sim_poses hold as for those replays and for
+ * ekf_sim_run, with which this call may alternate on one simulator: both advance the same tick and
+ * message counters.
+ * EKF_E_ARG, and nothing changes: a NULL simulator, T < 0, NULL wheel_cmd with T > 0,
+ * marker_stride > 64 (the replays' m_max limit), a pipeline handle on the one-marker route
+ * (ekf_get_assoc_route: EKF_ASSOC_MARKER). T == 0: EKF_OK. */
+int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd);
+
 /* With cfg.record: the last run's inputs as ekf_replay would take them — counts[T][F],
  * ids/actions[T][F][M], rel_xy[T][F][M][2] (M = marker_stride) — and odom[T][3] (t_odom_robot) and
  * truth[T][F][3] (θ, x, y). Synchronises. */
@@ -88,6 +109,14 @@ int ekf_sim_poses(ekf_sim_t s, double* odom, double* truth);
  * out[F] comes back. Needs no cfg.record. Synchronises; the filter is left alone as by ekf_eval.
  * EKF_E_ARG: a NULL simulator or out. */
 int ekf_sim_eval(ekf_sim_t s, ekf_eval_rec* out);
+
+/* ekf_eval_match (ekf.h) fed the same device-resident truth: each filter's true pose, its map
+ * landmarks[F][L][2] as the truth in any order (n_map = L), frame = the start pose. out[F];
+ * match_out[F] and match[F][N] (N = the handle's n_landmarks) are nullable. The truth never visits
+ * the host. Synchronises; the filter is left alone. EKF_E_ARG: a NULL simulator or out, max_dist
+ * negative or NaN. */
+int ekf_sim_eval_match(ekf_sim_t s, double max_dist, ekf_eval_rec* out, ekf_match_rec* match_out,
+                       int* match);
 
 #ifdef __cplusplus
 }
