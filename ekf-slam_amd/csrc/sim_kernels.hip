@@ -289,7 +289,9 @@ __global__ __launch_bounds__(64) void k_sim(SimArgs A) {
 }
 
 // ---- runs without SURVEY messages: every message sensed in parallel ----------------------------
-// Only the survey's sighted set carries sensing state from one message to the next; without it a
+// The sighted set: a landmark is sighted once a SURVEY message of this simulator has reported it;
+// NEAREST and ALL messages neither read nor write the set (k_sim above; synth._sense on the host).
+// Only that set carries sensing state from one message to the next; without a SURVEY message a
 // message's markers depend on its true pose alone. Pass 1 (k_sim_arcs, one wave per message and
 // filter: each message's tick scan; then k_sim_pose, one wave per filter: the products composed in
 // message order — the only sequential part) writes every message's true pose and odometry; pass 2 (k_sim_sense, one wave per message and filter, T·F in

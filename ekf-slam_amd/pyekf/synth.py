@@ -249,13 +249,24 @@ def _place_landmarks(n: int, half: float, seeds: np.ndarray, path: np.ndarray, c
 
 
 def _sense(drive: Drive, seeds, landmarks, truth, max_markers, max_range, sensor_sigma, shuffle,
-           n_delete, n_landmarks):
-    """Fake-sensor marker arrays for F filters → ids/actions [T, F, M], rel [T, F, M, 2], count."""
+           n_delete, n_landmarks, marker_stride=None):
+    """Fake-sensor marker arrays for F filters → ids/actions [T, F, M], rel [T, F, M, 2], count.
+
+    The sighted set: a landmark is sighted once a SURVEY message of this simulator has reported
+    it; NEAREST and ALL messages neither read nor write the set (include/ekf_sim.h,
+    EKF_SENSE_SURVEY). So without a SURVEY message a message's markers depend on its true pose
+    alone, which is what the device's parallel form rests on.
+
+    ``marker_stride``: the arrays' last dimension is M = max(the default, marker_stride), and the
+    noise of marker i of message t is normal draw 2·(t·M + i) (+1 for y) of that M, as the device's
+    ekf_sim_config.marker_stride. The entries from count to M are −1 / 0 / 0.0."""
     F, T = truth.shape[0], truth.shape[1]
     L = landmarks.shape[1]
     mall = int(np.any(drive.sense == SENSE_ALL))
     m = min(max_markers, L)
     M = (L if mall else m) + n_delete
+    if marker_stride is not None:
+        M = max(M, int(marker_stride))
     ids = np.full((T, F, M), -1, np.int32)
     act = np.zeros((T, F, M), np.int32)
     rel = np.zeros((T, F, M, 2))
@@ -304,7 +315,8 @@ def _sense(drive: Drive, seeds, landmarks, truth, max_markers, max_range, sensor
         rel[t, :, :W, 0] = np.where(valid, bx[rows, sel], 0.0)
         rel[t, :, :W, 1] = np.where(valid, by[rows, sel], 0.0)
         cnt[t] = k
-        sighted[np.broadcast_to(rows, sel.shape)[valid], sel[valid]] = True
+        if mode == SENSE_SURVEY:  # only a SURVEY message sights (k_sim, sim_kernels.hip)
+            sighted[np.broadcast_to(rows, sel.shape)[valid], sel[valid]] = True
         if n_delete:
             j = np.arange(n_delete, dtype=np.uint64)
             far = (rng_u64(seeds[:, None], _S_DELETE, np.uint64(t) * np.uint64(n_delete) + j)
@@ -364,7 +376,7 @@ class Swarm:
 
 def _generate(n_landmarks, drive: Drive, seeds, landmarks=None, half=None, *, max_markers=16,
               start_pose=(0.0, 0.0, -1.0), sensor_sigma=1e-3, slip=0.02, max_range=5.0,
-              shuffle=False, n_delete=0, clearance=0.3, n_map=None) -> Swarm:
+              shuffle=False, n_delete=0, clearance=0.3, n_map=None, marker_stride=None) -> Swarm:
     seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
     F = seeds.shape[0]
     if drive.start_pose is not None:
@@ -383,7 +395,8 @@ def _generate(n_landmarks, drive: Drive, seeds, landmarks=None, half=None, *, ma
                                     (F,) + np.shape(landmarks)[-2:]).copy()
     assert landmarks.shape[1] <= n_landmarks
     ids, act, rel, cnt, sighted = _sense(drive, seeds, landmarks, truth, max_markers, max_range,
-                                         sensor_sigma, shuffle, n_delete, n_landmarks)
+                                         sensor_sigma, shuffle, n_delete, n_landmarks,
+                                         marker_stride)
     return Swarm(n_landmarks, seeds, landmarks, wheel, ids, act, rel, cnt,
                  np.ascontiguousarray(truth.transpose(1, 0, 2)), drive.n_warm, sighted, cmd,
                  drive.sense.copy(), tuple(float(v) for v in start_pose))

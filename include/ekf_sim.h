@@ -44,7 +44,10 @@ extern "C" {
 typedef struct ekf_sim* ekf_sim_t;
 
 #define EKF_SENSE_NEAREST 0 /* the m nearest landmarks within max_range, nearest first */
-#define EKF_SENSE_SURVEY 1  /* within 2·max_range, not-yet-sighted first, never empty */
+#define EKF_SENSE_SURVEY 1  /* within 2·max_range, not-yet-sighted first, never empty. The sighted
+                             * set: a landmark is sighted once a SURVEY message of this simulator
+                             * has reported it; NEAREST and ALL messages neither read nor write
+                             * the set */
 #define EKF_SENSE_ALL 2     /* every landmark in id order, DELETE beyond max_range */
 
 typedef struct {

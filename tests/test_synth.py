@@ -4,6 +4,8 @@ CPU-only: these check the generator's own contract — counter-based seeding per
 warm-up sighting every landmark, the path clearance, and the marker semantics the reference's
 callbacks see (slam.cpp:205: only DELETE is skipped).
 """
+import hashlib
+
 import numpy as np
 
 from pyekf import synth
@@ -55,6 +57,31 @@ def test_circle_drive_sees_only_the_landmarks_near_it():
     """The plain circle (synth.synthetic) is why the survey exists: at N=1024 it sights ~35 ids."""
     sc = synth.synthetic(1024, 100)
     assert np.unique(sc.ids[sc.ids >= 0]).size < 64
+
+
+def _digest(obj, names):
+    h = hashlib.sha256()
+    for n in names:
+        a = np.ascontiguousarray(getattr(obj, n))
+        h.update(n.encode() + str(a.dtype).encode() + str(a.shape).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def test_survey_first_outputs_are_pinned():
+    """Only a SURVEY message sights a landmark (synth._sense; the device's rule). Workloads whose
+    SURVEY messages all come first do not depend on what later messages do to the set: these
+    SHA-256 digests of ids, actions, rel, count, truth, sighted and landmarks were computed with
+    the generator as it stood before that rule (every reported landmark sighted) and before the
+    marker_stride keyword, and hold unchanged."""
+    sw = ("ids", "actions", "rel", "count", "truth", "sighted", "landmarks")
+    sc = ("ids", "actions", "rel", "count", "truth", "landmarks")
+    assert _digest(synth.swarm(64, 2, 6), sw) == \
+        "06ccbb57627110c48835318024c40c20403f299701504702f14fb5229a90082a"
+    assert _digest(synth.swarm(128, 2, 4), sw) == \
+        "cf398bb00262abf6e563086bae7cd61bf9adf4bede09cdc6db316c2d59524384"
+    assert _digest(synth.basic_world(12), sc) == \
+        "c7555dc1ce9bded293297fbf73153dbaca3c3985454f1f38aec5d0823c46b15a"
 
 
 def test_basic_world_reports_every_landmark_with_delete_beyond_range():
