@@ -268,6 +268,7 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
   const char* serial_env = std::getenv("EKF_SERIAL");
   if (serial_env) h->serial = std::atoi(serial_env) != 0;
   if (const char* e = std::getenv("EKF_ASSOC_MSG")) h->assoc_msg = std::atoi(e) != 0;
+  if (const char* e = std::getenv("EKF_CHAIN_FAST")) h->chain_fast = std::atoi(e) != 0;
   {  // EKF_RESIDENT=0: the HBM pipeline at every size (tests compare the two)
     const char* e = std::getenv("EKF_RESIDENT");
     h->resident = cfg.dtype == EKF_F64 && h->n <= kResidentMaxN && !(e && std::atoi(e) == 0);
@@ -529,6 +530,16 @@ int ekf_get_decisions(ekf_t h, int f, int m, int* assoc_out, int* is_new_out) {
     if (assoc_out) assoc_out[i] = c.assoc_j[i];
     if (is_new_out) is_new_out[i] = c.assoc_new[i];
   }
+  return EKF_OK;
+}
+
+int ekf_chain_path_counts(ekf_t h, int f, unsigned long long* lean, unsigned long long* generic) {
+  if (!valid(h, f) || !lean || !generic) return EKF_E_ARG;
+  if (int rc = settle(h)) return rc;
+  FilterCtl c;
+  HIPCHK(hipMemcpy(&c, h->ctl + f, sizeof(FilterCtl), hipMemcpyDeviceToHost));
+  *lean = c.chain_steps[0];
+  *generic = c.chain_steps[1];
   return EKF_OK;
 }
 

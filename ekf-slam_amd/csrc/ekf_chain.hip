@@ -22,7 +22,7 @@
 // single-marker chunk.
 //
 // k_chain is the chunk loop; a chunk's phases, in execution order (every one __forceinline__ into
-// the kernel's one register allocation, except chain_wave0):
+// the kernel's one register allocation, except wave 0's two programs):
 //   issue_early_loads         kLook, staged: the image and the previous record → ChainLoads
 //   build_index_sets          A0: U and U'
 //   rebuild_block             A1, kLook: land_rebuild_operands (staged image, or its own gather and
@@ -30,7 +30,7 @@
 //                             wave 3: x_in[U]), rebuild_p_simple / _joseph, pick_predicted_pose
 //   gather_block              A1 otherwise: Σ_in[U, U], x[U] and the predicted pose from HBM
 //   fold_predict              A3: this chunk's predict on the block
-//   chain_wave0 .. 3          A2: the corrections; Z (wave 1), Y (wave 2), the rest of the block,
+//   chain_wave0 (_lean) .. 3  A2: the corrections; Z (wave 1), Y (wave 2), the rest of the block,
 //                             the posterior t_map_odom and the next predicted pose (wave 3)
 //   write_pend_patch          fp32: the final Σ[U, U] in fp64 for k_patch_stage
 //   write_record              ChunkRec, write-through
@@ -131,6 +131,9 @@ struct ChainSharedT {
   int pdone;  // steps wave 3 has applied outside the cross
   int any_init;  // a correction of this chunk initialised its landmark (slam.cpp:213-216)
   int zdone;     // Joseph: steps whose Z_c, Zv_c wave 1 has stored (wave 2 reads them)
+  // steps wave 0 has run in its lean and in its generic program during this launch (wave 0's
+  // lane 0 alone; added to FilterCtl::chain_steps once, at the launch's end)
+  unsigned n_lean, n_generic;
 };
 
 // Intra-workgroup hand-off through LDS (waves on different SIMDs; no s_barrier).
@@ -147,9 +150,18 @@ __device__ __forceinline__ void lds_wait_ge(const int* flag, int v) {
     __builtin_amdgcn_s_sleep(1);
 }
 
-// Wave 0's corrections (see k_chain, A2): a function of its own, so that its register allocation
-// is not the one of the kernel's four wave programs together (the shared allocation spilled
-// SGPRs, and their reloads sat in this loop). LDS through address-space-3 references.
+// Wave 0's corrections (see k_chain, A2): functions of their own, so that their register
+// allocation is not the one of the kernel's four wave programs together (the shared allocation
+// spilled SGPRs, and their reloads sat in this loop). LDS through address-space-3 references.
+//
+// Two programs from one body (wave0_steps): the generic one, chain_wave0, holds every case; the
+// lean one, chain_wave0_lean, holds the common case alone — a landmark already in the map, a valid
+// id, a finite nonsingular S, angles within normalize_angle_near's range — and neither the first
+// sighting's cos / sin, nor the generic normalize_angle, the re-done scalars, the skip's zeroing or
+// the status word: a third of the code, fewer blocks on the step's path and fewer registers to
+// save around the call. It never computes a rare case: it detects one and returns the index of
+// the first step it did not run, and the generic program resumes there (k_chain). Both evaluate
+// the one body's expressions in the one order, so a step has the same bits whichever ran it.
 template <bool J>
 using LdsChain = __attribute__((address_space(3))) ChainSharedT<J>;
 typedef __attribute__((address_space(3))) const MsgDesc LdsDesc;
@@ -168,12 +180,16 @@ __device__ __forceinline__ void lds_wait_ge3(const __attribute__((address_space(
 // J: a Joseph chunk (m ≤ kMaxJoseph). Every step then also subtracts V_c·K_cᵀ, V_c = Σ_c·Hᵀ − K_c·S_c
 // (slam.cpp:264-265's update as (I − KH)Σ(I − KH)ᵀ + K·R·Kᵀ expanded), always after the K_c·M_c term
 // — the order wave 3 uses, so an entry both waves compute has the same bits.
-template <bool J>
-__device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, int m, int nu,
-                                         double r_noise, unsigned seq) {
-  LdsChain<J>& sh = *shp;
+//
+// c0: the step to start at. What step c0 > 0 would hold in registers had the function run from
+// step 0 is all in LDS: wave 0 stores its cross (the next step's pk / pm) and x[U] every step,
+// and wave 3 stores the rest of the block with the same operands in the same order, so the block
+// after step c0 − 1 is whole once pdone ≥ c0. LEAN: only c0 = 0. Returns the first step not run
+// (the generic program: m).
+template <bool J, bool LEAN>
+__device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, int m, int nu,
+                                           double r_noise, unsigned seq) {
   constexpr int JM = ChainSharedT<J>::JM;
-  LdsDesc& d = *dp;
   const int lane = threadIdx.x & 63;
   (void)seq;  // (diagnostic stamps)
   // Lane ℓ carries row ℓ of the step's block columns (pk = Σ[ℓ, pA]) and column ℓ of its block
@@ -184,20 +200,25 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
   // them. Lanes ≥ |U| carry a clamped row and never store.
   const int lr = lane < kMaxU ? lane : kMaxU - 1;
   const int ul = sh.u[lr];
+  if (!LEAN && c0 > 0) {  // wave 3's step c0 − 1 outside the cross (the nx columns / rows below)
+    lds_wait_ge3(&sh.pdone, c0);
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  }
   double pk[5], pm[5];
   double xl = sh.xU[0][lr];
 #pragma unroll
   for (int a = 0; a < 5; ++a) {
-    const int col = a < 3 ? a : 3 + a - 3;  // pA of step 0 = {0, 1, 2, 3, 4}
+    const int col = a < 3 ? a : 3 + 2 * c0 + a - 3;  // pA of step c0 = {0, 1, 2, pj, pj + 1}
     pk[a] = sh.im.D[lr][col];
     pm[a] = sh.im.D[col][lr];
   }
   // Look-ahead operands of the next marker's cross (see the step): rn = Σ[ℓ, nx..nx+1] and
   // qn = Σ[nx..nx+1, ℓ] one step old, and the previous step's K (kp) and M (mp) of this lane.
+  // (A start at c0 > 0 reads them with step c0 − 1 applied and keeps step 0's kp = mp = 0.)
   double rn[2], qn[2], kp0 = 0.0, kp1 = 0.0, mp0 = 0.0, mp1 = 0.0, vp0 = 0.0, vp1 = 0.0;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int col = min(5 + j, kMaxU - 1);
+    const int col = min(5 + 2 * c0 + j, kMaxU - 1);
     rn[j] = sh.im.D[lr][col];
     qn[j] = sh.im.D[col][lr];
   }
@@ -209,35 +230,44 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
   // the marker's measurement and skip flag, read one step ahead (the descriptor and the skip list
   // are constant during the chunk): their LDS round trip stays off the step's dependent chain
   const bool noinit = (d.flags & kNoInit) != 0;
+  if (LEAN && noinit) return 0;  // (an association chunk: the generic program's)
   double zn0 = 0.0, zn1 = 0.0;
   int skn = 0;
-  if (m > 0) {
-    zn0 = d.z[0][0];
-    zn1 = d.z[0][1];
-    skn = sh.skip[0];
+  if (c0 < m) {
+    zn0 = d.z[c0][0];
+    zn1 = d.z[c0][1];
+    skn = sh.skip[c0];
   }
-  auto geometry = [&](int c) {
+  // → whether marker c is the lean program's (LEAN; always true otherwise): a valid id and a
+  // landmark that is in the map. If not, nothing of its geometry is computed.
+  auto geometry = [&](int c) -> bool {
     const int pj = 3 + 2 * c;
     const double pose[3] = {readlane_f64(xl, 0), readlane_f64(xl, 1), readlane_f64(xl, 2)};
     lx = readlane_f64(xl, pj);
     ly = readlane_f64(xl, pj + 1);
-    init = false;
-    // slam.cpp:213-216 (zn, skn: marker c); a wave-uniform test, so a scalar branch
-    if (__builtin_amdgcn_readfirstlane(!skn && !noinit && lx == 0.0 && ly == 0.0)) {
-      init = true;
-      sh.any_init = 1;
-      lx = pose[1] + zn0 * cos(zn1 + pose[0]);
-      ly = pose[2] + zn0 * sin(zn1 + pose[0]);
+    if constexpr (LEAN) {
+      // a skipped marker or a first sighting (slam.cpp:213-216): wave-uniform, a scalar branch
+      if (__builtin_amdgcn_readfirstlane(skn || (lx == 0.0 && ly == 0.0))) return false;
+    } else {
+      init = false;
+      // slam.cpp:213-216 (zn, skn: marker c); a wave-uniform test, so a scalar branch
+      if (__builtin_amdgcn_readfirstlane(!skn && !noinit && lx == 0.0 && ly == 0.0)) {
+        init = true;
+        sh.any_init = 1;
+        lx = pose[1] + zn0 * cos(zn1 + pose[0]);
+        ly = pose[2] + zn0 * sin(zn1 + pose[0]);
+      }
     }
     range_bearing(pose, lx, ly, zhat, H0, H1, &braw, &bok);
+    return true;
   };
-  if (m > 0) geometry(0);
-  for (int c = 0; c < m; ++c) {
+  if (c0 < m && !geometry(c0)) return c0;
+  for (int c = c0; c < m; ++c) {
     const int pj = 3 + 2 * c, nx = pj + 2;
     const bool more = c + 1 < m;
     EKF_STAMP(64 + 8 * c);
     const double z0 = zn0, z1 = zn1;
-    bool sk = skn != 0;
+    bool sk = !LEAN && skn != 0;  // (LEAN: geometry(c) let no skipped marker in)
     if (more) {  // marker c + 1's, for geometry(c + 1) and the next step
       zn0 = d.z[c + 1][0];
       zn1 = d.z[c + 1][1];
@@ -279,6 +309,7 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
       nv1 = normalize_angle_near(z1 - zhat[1], &nok);
       const bool good = !sk && bok && nok && inv2_ok(det, Si);
       if (!__builtin_amdgcn_readfirstlane(good)) {  // (uniform: every lane has the same scalars)
+        if constexpr (LEAN) return c;  // (nothing of step c is stored or published yet)
         if (!bok) zhat[1] = normalize_angle(braw);  // |θ| > π: the generic fmod path
         if (!sk && inv2(Sm, Si)) {
           nv0 = z0 - zhat[0];
@@ -353,22 +384,28 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
       }
     }
     const int jx = __builtin_amdgcn_readlane(ul, pj);  // sh.u[pj] (ul = sh.u[lane], pj < kMaxU)
+    (void)jx;  // (a first sighting's rows: the generic program's)
     EKF_STAMP(67 + 8 * c);
-    const double K0 = ka * Si[0] + kb * Si[2];  // K = Σ·Hᵀ·S⁻¹
-    const double K1 = ka * Si[1] + kb * Si[3];
+    // K = Σ·Hᵀ·S⁻¹ = ka·Si[0] + kb·Si[2], ka·Si[1] + kb·Si[3]. Which product the compiler fuses
+    // into the sum differed between the two programs (the lean one took ka's, 1e-12 in x after a
+    // drive): these sums of products and the two below are spelled out, the way the single
+    // program of before was compiled.
+    const double K0 = fma(kb, Si[2], ka * Si[0]);
+    const double K1 = fma(kb, Si[3], ka * Si[1]);
     // Joseph: V = Σ·Hᵀ − K·S of this lane's row (zero in exact arithmetic; the form's rounding)
-    const double V0 = J ? ka - (K0 * Sm_keep[0] + K1 * Sm_keep[2]) : 0.0;
-    const double V1 = J ? kb - (K0 * Sm_keep[1] + K1 * Sm_keep[3]) : 0.0;
+    const double V0 = J ? ka - fma(K0, Sm_keep[0], K1 * Sm_keep[2]) : 0.0;
+    const double V1 = J ? kb - fma(K0, Sm_keep[1], K1 * Sm_keep[3]) : 0.0;
     {
       double xt = xl;
-      xt = (init && ul == jx) ? lx : ((init && ul == jx + 1) ? ly : xt);
-      xt = xt + (K0 * nv0 + K1 * nv1);              // slam.cpp:261
+      if constexpr (!LEAN) xt = (init && ul == jx) ? lx : ((init && ul == jx + 1) ? ly : xt);
+      xt = xt + fma(K0, nv0, K1 * nv1);             // slam.cpp:261
       bool tok;                                     // slam.cpp:267 on lane 0, branch-free
       const double tn = normalize_angle_near(xt, &tok);
       const double xraw = xt;
       xt = lane == 0 ? tn : xt;
       // lane 0's θ beyond normalize_angle_near's range: the generic path (a scalar branch)
       if (__builtin_amdgcn_ballot_w64(!tok) & 1ull) {
+        if constexpr (LEAN) return c;  // (step c's first store is the one below)
         if (lane == 0) xt = normalize_angle(xraw);
       }
       xl = xt;
@@ -388,7 +425,7 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
         vd[0] = in ? V0 : 0.0;
         vd[1] = in ? V1 : 0.0;
         if (lane == 0)
-          for (int k = 0; k < 4; ++k) sh.Ss[cj][k] = sk ? 0.0 : Sm_keep[k];
+          for (int k = 0; k < 4; ++k) sh.Ss[cj][k] = !LEAN && sk ? 0.0 : Sm_keep[k];
       }
     }
     if (lane == 0) {
@@ -423,7 +460,9 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
           vx1[k] = sh.VU[cj][l][1];
         }
       }
-      geometry(c + 1);
+      // (LEAN, marker c + 1 not the lean program's: this step's cross update, which does not need
+      // that marker's geometry, then out)
+      const bool next_ok = geometry(c + 1);
       // wave 3's step c−1 writes outside this step's cross must land before this cross update
       // overwrites the nx columns / rows (waited for above already when c + 2 < m)
       if (c + 2 >= m && __builtin_amdgcn_readfirstlane(pd_early) < c) lds_wait_ge3(&sh.pdone, c);
@@ -454,9 +493,25 @@ __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int pb, 
       mp1 = mm1;
       vp0 = V0;
       vp1 = V1;
+      if (LEAN && !next_ok) return c + 1;
     }
     EKF_STAMP(70 + 8 * c);
   }
+  return m;
+}
+
+template <bool J>
+__device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int c0, int m, int nu,
+                                         double r_noise, unsigned seq) {
+  wave0_steps<J, false>(*shp, *dp, c0, m, nu, r_noise, seq);
+}
+template <bool J>
+__device__ __noinline__ int chain_wave0_lean(LdsChain<J>* shp, LdsDesc* dp, int m, int nu,
+                                             double r_noise, unsigned seq) {
+  // (arguments arrive in vector registers: said to be wave-uniform here, the step loop's control
+  // flow and addresses are scalar)
+  return wave0_steps<J, true>(*shp, *dp, 0, __builtin_amdgcn_readfirstlane(m),
+                              __builtin_amdgcn_readfirstlane(nu), readfirstlane_f64(r_noise), seq);
 }
 
 // The previous chunk's predict on the rebuild operands: v + α_i·Σ[0][j] +
@@ -1807,9 +1862,17 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     const bool pre_next = ci + 1 < nchunks;
     // this chunk's own record (waves 1–2 write Z, Y through; then the pend patch and the rest)
     ChunkRec* const rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
-    if (L.wv == 0)
-      chain_wave0<J>((LdsChain<J>*)(&sh), (LdsDesc*)(&d), 0, m, nu, A.r, seq);
-    else if (L.wv == 3)
+    if (L.wv == 0) {
+      // A.chain_fast (EKF_CHAIN_FAST=1): the lean program as far as the chunk's markers are common
+      // cases, the generic one from the first that is not; otherwise the generic one from step 0
+      int c = 0;
+      if (A.chain_fast) c = chain_wave0_lean<J>((LdsChain<J>*)(&sh), (LdsDesc*)(&d), m, nu, A.r, seq);
+      if (c < m) chain_wave0<J>((LdsChain<J>*)(&sh), (LdsDesc*)(&d), c, m, nu, A.r, seq);
+      if (tid == 0) {
+        sh.n_lean += static_cast<unsigned>(c);
+        sh.n_generic += static_cast<unsigned>(m - c);
+      }
+    } else if (L.wv == 3)
       chain_wave3(sh, d, A, ctl, fy, m, nu, L.ln, ci, nchunks, seq);
     else if (L.wv == 1)
       chain_wave1(sh, rec, m, nu, L.ln, seq);
@@ -1843,6 +1906,11 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     drain_stores();
     __syncthreads();
     if (tid == 0) epoch_store(A.sync + kSyncChain + f, pending);
+  }
+  // the launch's step counts (a filter's chain launches are ordered: plain loads and stores)
+  if (tid == 0 && (sh.n_lean | sh.n_generic)) {
+    ctl->chain_steps[0] += sh.n_lean;
+    ctl->chain_steps[1] += sh.n_generic;
   }
 }
 template <typename T>

@@ -73,6 +73,9 @@ struct alignas(16) FilterCtl {
   unsigned status;     // EKF_FLAG_* bits
   int assoc_j[kMaxAssoc];
   int assoc_new[kMaxAssoc];
+  // corrections k_chain's wave 0 has run in its lean and in its generic program since the last
+  // reset (ekf_chain_path_counts)
+  unsigned long long chain_steps[2];
 };
 
 // One posterior of the pose trace (ekf_trace_rec of include/ekf.h, the same 64 bytes): appended by

@@ -42,6 +42,7 @@ PassArgs<T> args(ekf_ctx* h, const MsgDesc* desc, int f0) {
   a.r = h->cfg.r_noise;
   a.gate = h->cfg.mah_gate;
   a.joseph = h->plan.joseph() ? 1 : 0;
+  a.chain_fast = h->chain_fast ? 1 : 0;
   a.trace = h->trace;
   a.trace_n = h->trace_n;
   a.trace_cap = h->trace_cap;

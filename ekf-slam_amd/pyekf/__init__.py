@@ -39,8 +39,8 @@ EXPORTS = [
     "ekf_set_joseph",
     "ekf_reset", "slam_reset",
     "ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear", "slam_replay_trace",
-    "ekf_profile_enable", "ekf_profile_read", "ekf_sigma_pass_bytes", "ekf_normalize_angle",
-    "ekf_debug_poison_lds",
+    "ekf_profile_enable", "ekf_profile_read", "ekf_sigma_pass_bytes", "ekf_chain_path_counts",
+    "ekf_normalize_angle", "ekf_debug_poison_lds",
     "slam_create", "slam_destroy", "slam_joint_states", "slam_markers", "slam_initial_pose",
     "slam_odom", "slam_map_odom", "slam_filter", "slam_replay", "slam_integrate_odometry",
     "lm_create", "lm_destroy", "lm_detect", "lm_fit_circles", "lm_check_circles",
@@ -58,7 +58,7 @@ TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_t
 EVAL_EXPORTS = ("ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval")
 MATCH_EXPORTS = ("ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match")
 LATER_EXPORTS = (TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident") + EVAL_EXPORTS +
-                 MATCH_EXPORTS)
+                 MATCH_EXPORTS + ("ekf_chain_path_counts",))
 EKF_MATCH_MAX_MAP = 1024
 EKF_EVAL_POSE_NOT_PD, EKF_EVAL_LM_NOT_PD = 1, 2
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
@@ -192,6 +192,8 @@ def lib():
             "ekf_reset": (_i, [_vp, _i]),
             "slam_reset": (_i, [_vp]),
             "ekf_trace_enable": (_i, [_vp, _i]),
+            "ekf_chain_path_counts": (_i, [_vp, _i, C.POINTER(C.c_ulonglong),
+                                           C.POINTER(C.c_ulonglong)]),
             "ekf_trace_count": (_i, [_vp, _i, C.POINTER(C.c_longlong)]),
             "ekf_trace_read": (_i, [_vp, _i, C.c_longlong, _i, _vp, _ip]),
             "ekf_trace_clear": (_i, [_vp, _i]),
@@ -496,6 +498,15 @@ class EKF:
     def trace_enable(self, capacity):
         """Keep up to `capacity` records per filter (0: off and freed). Reallocates and clears."""
         _check(lib().ekf_trace_enable(self.h, int(capacity)), "ekf_trace_enable")
+
+    def chain_path_counts(self, f=0):
+        """(lean, generic): corrections the chain kernel's sequential wave has run for filter f in
+        its common-case program (EKF_CHAIN_FAST=1) and in its generic one since the handle's
+        creation or last reset (by default all of them in the generic one)."""
+        a, b = C.c_ulonglong(0), C.c_ulonglong(0)
+        _check(lib().ekf_chain_path_counts(self.h, f, C.byref(a), C.byref(b)),
+               "ekf_chain_path_counts")
+        return a.value, b.value
 
     def trace_count(self, f=0) -> int:
         """Records appended to filter f's trace (those beyond the capacity are only counted)."""

@@ -463,6 +463,16 @@ int ekf_profile_read(ekf_t h, int kernel, long long* launches, double* total_ms)
 /* Bytes the Σ pass must move per launch for the current handle: fp32 2·n²·w·F (Σ_in read, Σ_out
  * written); fp64 (n(n+1)/2 + n²)·w·F (the symmetric pass reads Σ_in's upper triangle). */
 double ekf_sigma_pass_bytes(ekf_t h, int filters_in_launch);
+/* Corrections the chain kernel (pipeline handles, known ids and the one-marker association route)
+ * has run for `filter` since its creation or last ekf_reset, by the program of its sequential
+ * wave that ran them: `lean` holds the common case alone (a mapped landmark, a valid id, a
+ * nonsingular S, angles near (-π, π]) and hands a chunk over at the first marker that is anything
+ * else; `generic` holds every case. Their sum is the corrections the kernel was given, skipped
+ * ones included. The lean program is opt-in (EKF_CHAIN_FAST=1, read at ekf_create); by default
+ * every correction runs in the generic program. Bit-identical either way. Synchronises. EKF_E_ARG: NULL arguments or a
+ * filter out of range. */
+int ekf_chain_path_counts(ekf_t h, int filter, unsigned long long* lean,
+                          unsigned long long* generic);
 
 /* ---- diagnostics ---- */
 /* Fill every CU's LDS on `device` with a NaN bit pattern (default stream, synchronising): LDS then

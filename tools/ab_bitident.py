@@ -4,7 +4,8 @@
 
 Each library runs the same replays in its own child process (the headline fp32 N = 1024 device
 replay from an fp64 survey, fp64 N = 1024, messages of two chunks, the Joseph form, the rebuild
-without staged operands, the Joseph form in fp32 and under unknown association, four filters with
+without staged operands, wave 0's lean program (EKF_CHAIN_FAST=1), the Joseph form in
+fp32 and under unknown association, four filters with
 event hand-offs, unknown association and its routes: one marker per launch, one workgroup, three
 on each transport, a map that fills, messages of two chunks; the resident kernel: full maps in each
 register layout, known ids and association, a map that fills, the Joseph form, a ragged 48-filter
@@ -29,7 +30,7 @@ def child(tag):
 
     def env(**kv):
         for k in ("EKF_SERIAL", "EKF_DEVSYNC", "EKF_STAGE", "EKF_CU_SPLIT", "EKF_RESIDENT",
-                  "EKF_AM_XCD", "EKF_ASSOC_MSG"):
+                  "EKF_AM_XCD", "EKF_ASSOC_MSG", "EKF_CHAIN_FAST"):
             os.environ.pop(k, None)
         os.environ.update(kv)
 
@@ -99,6 +100,18 @@ def child(tag):
     for name, dt in (("nostage64", pyekf.EKF_F64), ("nostage32", pyekf.EKF_F32)):
         env(EKF_STAGE="0")
         e = pyekf.EKF(n_landmarks=96, dtype=dt)
+        e.replay(sc.count[:, None], sc.rel[:, None], odom[:, None], ids=sc.ids[:, None],
+                 actions=sc.actions[:, None])
+        keep(name, e)
+        e.close()
+    # ... common-case corrections in wave 0's lean program, the generic one resumed in mid-chunk
+    # at each first sighting (EKF_CHAIN_FAST=1; a library from before the two programs ignores
+    # the switch) ...
+    for name, dt, jo in (("lean64", pyekf.EKF_F64, False), ("lean32", pyekf.EKF_F32, False),
+                         ("lean_joseph32", pyekf.EKF_F32, True)):
+        env(EKF_CHAIN_FAST="1")
+        e = pyekf.EKF(n_landmarks=96, dtype=dt)
+        e.set_joseph(jo)
         e.replay(sc.count[:, None], sc.rel[:, None], odom[:, None], ids=sc.ids[:, None],
                  actions=sc.actions[:, None])
         keep(name, e)
