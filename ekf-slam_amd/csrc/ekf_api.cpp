@@ -29,41 +29,52 @@ int load_and_plan(ekf_ctx* h, int assoc_mode, int m_max, const int* counts, cons
   return EKF_OK;
 }
 
-// ---- gather and score (ekf_eval.hip): one device buffer per call, carved 16 bytes at a time ----
+// ---- gather and score (ekf_eval.hip): one device buffer per call (eval_buf), carved up ----
 
-size_t up16(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
-// A scoring launch with start / stop events on its dispatch when profiling (ekf_profile_read).
-template <typename Fn>
-hipError_t timed_eval(ekf_ctx* h, ProfSlot kind, Fn fn) {
-  auto take = [&]() -> hipEvent_t {
-    hipEvent_t e = nullptr;
-    if (!h->pool.empty()) {
-      e = h->pool.back();
-      h->pool.pop_back();
-    } else if (hipEventCreate(&e) != hipSuccess) {
-      e = nullptr;
-    }
-    return e;
-  };
-  hipEvent_t a = h->prof ? take() : nullptr, b = h->prof ? take() : nullptr;
-  if (!a || !b) return fn(nullptr, nullptr);
-  const hipError_t e = fn(a, b);
-  h->pe[kind].start.push_back(a);
-  h->pe[kind].stop.push_back(b);
-  return e;
-}
-
-int eval_reserve(ekf_ctx* h, size_t bytes) {
-  if (bytes <= h->eval_cap) return EKF_OK;
-  void* p = nullptr;
-  if (hipMalloc(&p, bytes) != hipSuccess) {
-    (void)hipGetLastError();  // (the launchers return hipGetLastError())
-    return EKF_E_NOMEM;
+// A call's pieces of eval_buf in order, each starting on 16 bytes. Size first, then carve: a call
+// runs its takes twice, over a null base to size the buffer (`off` ends as the bytes they need; the
+// callers have settled, so nothing in flight reads a buffer that growth frees), then over it.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  template <typename T>
+  T* take(size_t n) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += (n * sizeof(T) + 15) / 16 * 16;
+    return p;
   }
-  if (h->eval_buf) hipFree(h->eval_buf);
-  h->eval_buf = p;
-  h->eval_cap = bytes;
+};
+
+// The truth of ekf_eval / ekf_eval_match: from the host (h_pose [F][3], h_lm [F][n_map][2]) or,
+// with h_pose NULL, on the device (d_pose / d_lm).
+struct TruthSrc {
+  const double *h_pose, *h_lm, *d_pose;
+  size_t pose_stride;
+  const double* d_lm;
+  int n_map;
+  const double* frame;
+  double *up_pose = nullptr, *up_lm = nullptr;  // a host truth's place in eval_buf
+  void carve(Carver& c, size_t F) {
+    if (!h_pose) return;
+    up_pose = c.take<double>(F * 3);
+    if (n_map > 0) up_lm = c.take<double>(F * n_map * 2);
+  }
+};
+
+// ... uploaded if it is the host's, and as the kernels take it.
+int eval_truth(const TruthSrc& s, size_t F, EvalTruth* t) {
+  if (s.h_pose) {
+    HIPCHK(hipMemcpy(s.up_pose, s.h_pose, F * 3 * sizeof(double), hipMemcpyHostToDevice));
+    if (s.n_map > 0)
+      HIPCHK(hipMemcpy(s.up_lm, s.h_lm, F * s.n_map * 2 * sizeof(double), hipMemcpyHostToDevice));
+  }
+  *t = EvalTruth{};
+  t->pose = s.h_pose ? s.up_pose : s.d_pose;
+  t->pose_stride = s.h_pose ? 3 : s.pose_stride;
+  t->lm = s.n_map <= 0 ? nullptr : s.h_pose ? s.up_lm : s.d_lm;
+  t->n_map = s.n_map;
+  t->has_frame = s.frame != nullptr;
+  for (int k = 0; k < 3; ++k) t->frame[k] = s.frame ? s.frame[k] : 0.0;
   return EKF_OK;
 }
 
@@ -75,12 +86,12 @@ int eval_args(ekf_ctx* h, int* d_par, int f0, EvalArgs* a) {
   HIPCHK(hipMemcpy(d_par, par.data(), par.size() * sizeof(int), hipMemcpyHostToDevice));
   *a = EvalArgs{};
   for (int p = 0; p < 2; ++p) {
-    a->sig[p] = h->sig[p];
-    a->x[p] = h->x[p];
+    a->sig[p] = h->sig[p].get();
+    a->x[p] = h->x[p].get();
   }
   a->sig_stride = h->sig_stride;
   a->x_stride = h->x_stride;
-  a->ctl = h->ctl;
+  a->ctl = h->ctl.get();
   a->parity = d_par;
   a->N = h->cfg.n_landmarks;
   a->ld = h->ld;
@@ -88,103 +99,50 @@ int eval_args(ekf_ctx* h, int* d_par, int f0, EvalArgs* a) {
   return EKF_OK;
 }
 
-// ekf_eval: the truth from the host (h_pose [F][3], h_lm [F][n_map][2]) or, with h_pose NULL,
-// from the device (d_pose / d_lm). Arguments checked by the callers.
-int eval_run(ekf_ctx* h, const double* h_pose, const double* h_lm, const double* d_pose,
-             size_t pose_stride, const double* d_lm, int n_map, const double* frame,
-             ekf_eval_rec* out) {
+// ekf_eval and, `matched`, ekf_eval_match (the truth map in any order, slots matched within
+// max_dist). Arguments checked by the callers.
+int eval_run(ekf_ctx* h, TruthSrc src, bool matched, double max_dist, ekf_eval_rec* out,
+             ekf_match_rec* match_out, int* match) {
   if (int rc = settle(h)) return rc;
   hipSetDevice(h->cfg.device);
-  const size_t F = static_cast<size_t>(h->F);
-  const size_t par_b = up16(F * sizeof(int)), rec_b = F * sizeof(EvalRec);
-  const size_t pose_b = h_pose ? up16(F * 3 * sizeof(double)) : 0;
-  const size_t lm_b = h_pose && n_map > 0 ? up16(F * n_map * 2 * sizeof(double)) : 0;
-  if (int rc = eval_reserve(h, par_b + rec_b + pose_b + lm_b)) return rc;
-  char* base = static_cast<char*>(h->eval_buf);
-  int* par = reinterpret_cast<int*>(base);
-  EvalRec* rec = reinterpret_cast<EvalRec*>(base + par_b);
-  EvalTruth t{};
-  if (h_pose) {
-    double* up = reinterpret_cast<double*>(base + par_b + rec_b);
-    HIPCHK(hipMemcpy(up, h_pose, F * 3 * sizeof(double), hipMemcpyHostToDevice));
-    d_pose = up;
-    pose_stride = 3;
-    d_lm = nullptr;
-    if (n_map > 0) {
-      double* ul = reinterpret_cast<double*>(base + par_b + rec_b + pose_b);
-      HIPCHK(hipMemcpy(ul, h_lm, F * n_map * 2 * sizeof(double), hipMemcpyHostToDevice));
-      d_lm = ul;
+  const size_t F = static_cast<size_t>(h->F), N = static_cast<size_t>(h->cfg.n_landmarks);
+  int* par = nullptr;
+  MatchOut o{};
+  auto carve = [&](char* base) {
+    Carver c{base};
+    par = c.take<int>(F);
+    o.rec = c.take<EvalRec>(F);
+    if (matched) {
+      o.mrec = c.take<MatchRec>(F);
+      o.match = c.take<int>(F * N);
     }
-  }
-  t.pose = d_pose;
-  t.pose_stride = pose_stride;
-  t.lm = n_map > 0 ? d_lm : nullptr;
-  t.n_map = n_map;
-  t.has_frame = frame != nullptr;
-  for (int k = 0; k < 3; ++k) t.frame[k] = frame ? frame[k] : 0.0;
+    src.carve(c, F);
+    return c.off;
+  };
+  if (int rc = h->eval_buf.reserve(carve(nullptr))) return rc;
+  carve(h->eval_buf.get());
+  EvalTruth t;
+  if (int rc = eval_truth(src, F, &t)) return rc;
   EvalArgs a;
   if (int rc = eval_args(h, par, 0, &a)) return rc;
-  HIPCHK(timed_eval(h, kProfEval, [&](hipEvent_t e0, hipEvent_t e1) {
+  const hipStream_t st = h->stream.get();
+  const int rc = timed(h, matched ? kProfEvalMatch : kProfEval, [&](hipEvent_t e0, hipEvent_t e1) {
     return by_dtype(h, [&](auto tag) {
-      return launch_eval<decltype(tag)>(a, t, rec, h->F, h->stream, e0, e1);
+      using T = decltype(tag);
+      return matched ? launch_eval_match<T>(a, t, max_dist * max_dist, o, h->F, st, e0, e1)
+                     : launch_eval<T>(a, t, o.rec, h->F, st, e0, e1);
     });
-  }));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(out, rec, rec_b, hipMemcpyDeviceToHost));
+  });
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipMemcpy(out, o.rec, F * sizeof(EvalRec), hipMemcpyDeviceToHost));
+  if (match_out) HIPCHK(hipMemcpy(match_out, o.mrec, F * sizeof(MatchRec), hipMemcpyDeviceToHost));
+  if (match) HIPCHK(hipMemcpy(match, o.match, F * N * sizeof(int), hipMemcpyDeviceToHost));
   return EKF_OK;
 }
 
 bool eval_args_ok(const ekf_ctx* h, const void* pose, const void* lm, int n_map, const void* out) {
   return h && pose && out && n_map >= 0 && n_map <= h->cfg.n_landmarks && (lm || n_map == 0);
-}
-
-// ekf_eval_match: the truth as eval_run takes it (from the host, or with h_pose NULL on the
-// device), in any order. Arguments checked by the callers.
-int eval_match_run(ekf_ctx* h, const double* h_pose, const double* h_lm, const double* d_pose,
-                   size_t pose_stride, const double* d_lm, int n_map, const double* frame,
-                   double max_dist, ekf_eval_rec* out, ekf_match_rec* match_out, int* match) {
-  if (int rc = settle(h)) return rc;
-  hipSetDevice(h->cfg.device);
-  const size_t F = static_cast<size_t>(h->F), N = static_cast<size_t>(h->cfg.n_landmarks);
-  const size_t par_b = up16(F * sizeof(int)), rec_b = F * sizeof(EvalRec),
-               mrec_b = F * sizeof(MatchRec), match_b = up16(F * N * sizeof(int));
-  const size_t pose_b = h_pose ? up16(F * 3 * sizeof(double)) : 0;
-  const size_t lm_b = h_pose ? up16(F * n_map * 2 * sizeof(double)) : 0;
-  if (int rc = eval_reserve(h, par_b + rec_b + mrec_b + match_b + pose_b + lm_b)) return rc;
-  char* base = static_cast<char*>(h->eval_buf);
-  MatchOut o{};
-  o.rec = reinterpret_cast<EvalRec*>(base + par_b);
-  o.mrec = reinterpret_cast<MatchRec*>(base + par_b + rec_b);
-  o.match = reinterpret_cast<int*>(base + par_b + rec_b + mrec_b);
-  if (h_pose) {
-    double* up = reinterpret_cast<double*>(base + par_b + rec_b + mrec_b + match_b);
-    double* ul = reinterpret_cast<double*>(base + par_b + rec_b + mrec_b + match_b + pose_b);
-    HIPCHK(hipMemcpy(up, h_pose, F * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ul, h_lm, F * n_map * 2 * sizeof(double), hipMemcpyHostToDevice));
-    d_pose = up;
-    pose_stride = 3;
-    d_lm = ul;
-  }
-  EvalTruth t{};
-  t.pose = d_pose;
-  t.pose_stride = pose_stride;
-  t.lm = d_lm;
-  t.n_map = n_map;
-  t.has_frame = frame != nullptr;
-  for (int k = 0; k < 3; ++k) t.frame[k] = frame ? frame[k] : 0.0;
-  EvalArgs a;
-  if (int rc = eval_args(h, reinterpret_cast<int*>(base), 0, &a)) return rc;
-  const double gate2 = max_dist * max_dist;
-  HIPCHK(timed_eval(h, kProfEvalMatch, [&](hipEvent_t e0, hipEvent_t e1) {
-    return by_dtype(h, [&](auto tag) {
-      return launch_eval_match<decltype(tag)>(a, t, gate2, o, h->F, h->stream, e0, e1);
-    });
-  }));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(out, o.rec, rec_b, hipMemcpyDeviceToHost));
-  if (match_out) HIPCHK(hipMemcpy(match_out, o.mrec, mrec_b, hipMemcpyDeviceToHost));
-  if (match) HIPCHK(hipMemcpy(match, o.match, F * N * sizeof(int), hipMemcpyDeviceToHost));
-  return EKF_OK;
 }
 
 // (max_dist: not negative and not NaN; +∞ is valid)
@@ -199,14 +157,15 @@ int ekfslam::eval_match_device(ekf_t h, const double* d_pose, size_t pose_stride
                                const double* d_lm, int n_map, const double* frame, double max_dist,
                                ekf_eval_rec* out, ekf_match_rec* match_out, int* match) {
   if (!match_args_ok(h, d_pose, d_lm, n_map, max_dist, out)) return EKF_E_ARG;
-  return eval_match_run(h, nullptr, nullptr, d_pose, pose_stride, d_lm, n_map, frame, max_dist, out,
-                        match_out, match);
+  return eval_run(h, {nullptr, nullptr, d_pose, pose_stride, d_lm, n_map, frame}, true, max_dist,
+                  out, match_out, match);
 }
 
 int ekfslam::eval_device(ekf_t h, const double* d_pose, size_t pose_stride, const double* d_lm,
                          int n_map, const double* frame, ekf_eval_rec* out) {
   if (!eval_args_ok(h, d_pose, d_lm, n_map, out)) return EKF_E_ARG;
-  return eval_run(h, nullptr, nullptr, d_pose, pose_stride, d_lm, n_map, frame, out);
+  return eval_run(h, {nullptr, nullptr, d_pose, pose_stride, d_lm, n_map, frame}, false, 0.0, out,
+                  nullptr, nullptr);
 }
 
 extern "C" {
@@ -261,7 +220,7 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
   h->km_stride = static_cast<size_t>(kMaxKW) * h->ldk;
   h->held.assign(h->F, 0);
   auto fail = [&](int rc) {
-    ekf_destroy(h);
+    ekf_destroy(h);  // (the members release what exists by then)
     return rc;
   };
   if (hipSetDevice(cfg.device) != hipSuccess) return fail(EKF_E_HIP);
@@ -273,11 +232,8 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
     const char* e = std::getenv("EKF_RESIDENT");
     h->resident = cfg.dtype == EKF_F64 && h->n <= kResidentMaxN && !(e && std::atoi(e) == 0);
   }
-  if (create_streams(h) != EKF_OK ||
-      hipEventCreateWithFlags(&h->ev_chain, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_sig[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev_sig[1], hipEventDisableTiming) != hipSuccess)
+  if (create_streams(h) || h->ev_chain.create() || h->ev_join.create() || h->ev_sig[0].create() ||
+      h->ev_sig[1].create())
     return fail(EKF_E_HIP);
   // Many filters (no CU split, so event hand-offs): the Σ pass's waves hold every CU a chain or a
   // factor kernel needs, so nothing overlaps it anyway; one stream turns the two
@@ -286,23 +242,18 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
   if (!serial_env && !h->devsync && h->F > kCuSplitMaxFilters) h->serial = true;
   h->am_route = am_route(h, false);
   h->am_route_j = am_route(h, true);
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->fatal_h), 64,
-                    hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-    return fail(EKF_E_NOMEM);
-  *h->fatal_h = 0;
-  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fatal_d), h->fatal_h, 0) != hipSuccess)
+  if (int rc = h->fatal_h.reserve(64 / sizeof(unsigned))) return fail(rc);
+  *h->fatal_h.get() = 0;
+  if (hipHostGetDevicePointer(reinterpret_cast<void**>(&h->fatal_d), h->fatal_h.get(), 0) !=
+      hipSuccess)
     return fail(EKF_E_HIP);
-  const size_t sig_bytes = h->sig_stride * h->F * h->w;
-  for (int p = 0; p < 2; ++p) {
-    if (hipMalloc(&h->sig[p], sig_bytes) != hipSuccess) return fail(EKF_E_NOMEM);
-    if (hipMalloc(&h->x[p], h->x_stride * h->F * sizeof(double)) != hipSuccess)
-      return fail(EKF_E_NOMEM);
-  }
-  const size_t km_bytes = h->km_stride * h->F * h->w;
-  if (hipMalloc(&h->kcat, km_bytes) != hipSuccess) return fail(EKF_E_NOMEM);
-  if (hipMalloc(&h->mcat, km_bytes) != hipSuccess) return fail(EKF_E_NOMEM);
-  if (hipMalloc(&h->ctl, sizeof(FilterCtl) * h->F) != hipSuccess) return fail(EKF_E_NOMEM);
-  if (hipMalloc(&h->rec, 2 * sizeof(ChunkRec) * h->F) != hipSuccess) return fail(EKF_E_NOMEM);
+  const size_t F = static_cast<size_t>(h->F);
+  const size_t sig_bytes = h->sig_stride * F * h->w, km_bytes = h->km_stride * F * h->w;
+  for (int p = 0; p < 2; ++p)
+    if (h->sig[p].reserve(sig_bytes) || h->x[p].reserve(h->x_stride * F)) return fail(EKF_E_NOMEM);
+  if (h->kcat.reserve(km_bytes) || h->mcat.reserve(km_bytes) || h->ctl.reserve(F) ||
+      h->rec.reserve(2 * F))
+    return fail(EKF_E_NOMEM);
   // staged rebuild operands (EKF_STAGE=0: every kLook chain gathers its own, tests compare the two)
   // The same many-filter handles skip it by default (EKF_STAGE=1 keeps it): there every message's
   // k_patch_stage runs on the serial critical path (≈ 18 µs for 512 filters), more than the chains'
@@ -313,34 +264,33 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
   const bool stage_on = stage_env ? std::atoi(stage_env) != 0
                                   : (h->devsync || h->F <= kCuSplitMaxFilters);
   if (stage_on) {
-    if (hipMalloc(&h->stage, stage_bytes) != hipSuccess) return fail(EKF_E_NOMEM);
-    if (hipMemset(h->stage, 0, stage_bytes) != hipSuccess) return fail(EKF_E_HIP);
+    if (int rc = h->stage.reserve(stage_bytes)) return fail(rc);
+    if (hipMemset(h->stage.get(), 0, stage_bytes) != hipSuccess) return fail(EKF_E_HIP);
   }
   h->plan.init(h->F, cfg.n_landmarks, h->resident, stage_on);
-  const size_t sync_bytes = sizeof(unsigned) * (kSyncChain + static_cast<size_t>(h->F));
-  if (hipMalloc(&h->sync, sync_bytes) != hipSuccess) return fail(EKF_E_NOMEM);
-  if (hipMemset(h->sync, 0, sync_bytes) != hipSuccess) return fail(EKF_E_HIP);
-  h->ddesc_cap = std::max(kDescInit, static_cast<size_t>(h->F) * 4);
-  if (hipMalloc(&h->ddesc, sizeof(MsgDesc) * h->ddesc_cap) != hipSuccess) return fail(EKF_E_NOMEM);
-  for (int i = 0; i < kRing; ++i)
-    if (hipEventCreateWithFlags(&h->ring[i].ev, hipEventDisableTiming) != hipSuccess)
-      return fail(EKF_E_HIP);
-  if (int rc = reserve_upload(h, h->ddesc_cap)) return fail(rc);  // every pinned slot up front
+  if (int rc = h->sync.reserve(kSyncChain + F)) return fail(rc);
+  if (hipMemset(h->sync.get(), 0, sizeof(unsigned) * h->sync.capacity()) != hipSuccess)
+    return fail(EKF_E_HIP);
+  if (int rc = h->ddesc.reserve(std::max(kDescInit, F * 4))) return fail(rc);
+  for (StageSlot& sl : h->ring)
+    if (int rc = sl.ev.create()) return fail(rc);
+  // every pinned slot up front
+  if (int rc = reserve_upload(h, h->ddesc.capacity())) return fail(rc);
   // Σ₀ = diag(0,0,0, init_var·I_2N), state = 0 (slam.cpp:127-132, :674)
   for (int p = 0; p < 2; ++p) {
-    if (hipMemsetAsync(h->sig[p], 0, sig_bytes, h->stream) != hipSuccess) return fail(EKF_E_HIP);
-    if (hipMemsetAsync(h->x[p], 0, h->x_stride * h->F * sizeof(double), h->stream) != hipSuccess)
+    if (hipMemsetAsync(h->sig[p].get(), 0, sig_bytes, h->stream.get()) != hipSuccess ||
+        hipMemsetAsync(h->x[p].get(), 0, h->x_stride * F * sizeof(double), h->stream.get()) !=
+            hipSuccess)
       return fail(EKF_E_HIP);
   }
   // chunk records start zeroed: no kernel ever sees a previous process's bytes, whatever the
   // stream interleaving
-  if (hipMemsetAsync(h->rec, 0, 2 * sizeof(ChunkRec) * h->F, h->stream) != hipSuccess)
+  if (hipMemsetAsync(h->rec.get(), 0, 2 * sizeof(ChunkRec) * F, h->stream.get()) != hipSuccess ||
+      hipMemsetAsync(h->kcat.get(), 0, km_bytes, h->stream.get()) != hipSuccess ||
+      hipMemsetAsync(h->mcat.get(), 0, km_bytes, h->stream.get()) != hipSuccess ||
+      hipMemsetAsync(h->ctl.get(), 0, sizeof(FilterCtl) * F, h->stream.get()) != hipSuccess)
     return fail(EKF_E_HIP);
-  if (hipMemsetAsync(h->kcat, 0, km_bytes, h->stream) != hipSuccess ||
-      hipMemsetAsync(h->mcat, 0, km_bytes, h->stream) != hipSuccess ||
-      hipMemsetAsync(h->ctl, 0, sizeof(FilterCtl) * h->F, h->stream) != hipSuccess)
-    return fail(EKF_E_HIP);
-  if (init_diag(h, h->sig[0], h->F) || hipStreamSynchronize(h->stream) != hipSuccess)
+  if (init_diag(h, h->sig[0].get(), h->F) || hipStreamSynchronize(h->stream.get()) != hipSuccess)
     return fail(EKF_E_HIP);
   *out = h;
   return EKF_OK;
@@ -349,47 +299,8 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
 int ekf_destroy(ekf_t h) {
   if (!h) return EKF_E_ARG;
   hipSetDevice(h->cfg.device);
-  if (h->bulk) hipStreamSynchronize(h->bulk);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (int p = 0; p < 2; ++p) {
-    if (h->sig[p]) hipFree(h->sig[p]);
-    if (h->x[p]) hipFree(h->x[p]);
-  }
-  if (h->kcat) hipFree(h->kcat);
-  if (h->mcat) hipFree(h->mcat);
-  if (h->ctl) hipFree(h->ctl);
-  if (h->rec) hipFree(h->rec);
-  if (h->stage) hipFree(h->stage);
-  if (h->ddesc) hipFree(h->ddesc);
-  if (h->trace) hipFree(h->trace);
-  if (h->trace_n) hipFree(h->trace_n);
-  if (h->eval_buf) hipFree(h->eval_buf);
-  for (PlanState* p : h->dstate)
-    if (p) hipFree(p);
-  if (h->hstate) hipHostFree(h->hstate);
-  if (h->odom_d) hipFree(h->odom_d);
-  if (h->odom_h) hipHostFree(h->odom_h);
-  if (h->ev_odom) hipEventDestroy(h->ev_odom);
-  if (h->fatal_h) hipHostFree(h->fatal_h);
-  if (h->am.hist) hipFree(h->am.hist);
-  if (h->am.cur) hipFree(h->am.cur);
-  if (h->am.gran) hipFree(h->am.gran);
-  for (int i = 0; i < kRing; ++i) {
-    if (h->ring[i].p) hipHostFree(h->ring[i].p);
-    if (h->ring[i].ev) hipEventDestroy(h->ring[i].ev);
-  }
-  for (auto& pe : h->pe) {
-    for (auto e : pe.start) hipEventDestroy(e);
-    for (auto e : pe.stop) hipEventDestroy(e);
-  }
-  for (auto e : h->pool) hipEventDestroy(e);
-  if (h->ev_chain) hipEventDestroy(h->ev_chain);
-  if (h->ev_join) hipEventDestroy(h->ev_join);
-  if (h->sync) hipFree(h->sync);
-  for (hipEvent_t e : h->ev_sig)
-    if (e) hipEventDestroy(e);
-  if (h->bulk) hipStreamDestroy(h->bulk);
-  if (h->stream) hipStreamDestroy(h->stream);
+  if (h->bulk.get()) hipStreamSynchronize(h->bulk.get());
+  if (h->stream.get()) hipStreamSynchronize(h->stream.get());
   delete h;
   return EKF_OK;
 }
@@ -483,8 +394,9 @@ int ekf_replay(ekf_t h, int assoc_mode, int T, int m_max, const int* counts, con
       if (rc) return rc;
       if (drain(h)) return EKF_E_HIP;
       for (size_t f = 0; f < F; ++f)
-        HIPCHK(hipMemcpy(out_pose + 3 * (F * t + f), h->x[h->plan.parity(f)] + f * h->x_stride,
-                         3 * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out_pose + 3 * (F * t + f),
+                         h->x[h->plan.parity(f)].get() + f * h->x_stride, 3 * sizeof(double),
+                         hipMemcpyDeviceToHost));
     }
   }
   return submit(h);
@@ -525,7 +437,7 @@ int ekf_get_decisions(ekf_t h, int f, int m, int* assoc_out, int* is_new_out) {
   if (!valid(h, f) || m < 0 || m > kMaxAssoc) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;
   FilterCtl c;
-  HIPCHK(hipMemcpy(&c, h->ctl + f, sizeof(FilterCtl), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&c, h->ctl.get() + f, sizeof(FilterCtl), hipMemcpyDeviceToHost));
   for (int i = 0; i < m; ++i) {
     if (assoc_out) assoc_out[i] = c.assoc_j[i];
     if (is_new_out) is_new_out[i] = c.assoc_new[i];
@@ -537,7 +449,7 @@ int ekf_chain_path_counts(ekf_t h, int f, unsigned long long* lean, unsigned lon
   if (!valid(h, f) || !lean || !generic) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;
   FilterCtl c;
-  HIPCHK(hipMemcpy(&c, h->ctl + f, sizeof(FilterCtl), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&c, h->ctl.get() + f, sizeof(FilterCtl), hipMemcpyDeviceToHost));
   *lean = c.chain_steps[0];
   *generic = c.chain_steps[1];
   return EKF_OK;
@@ -645,13 +557,13 @@ int ekf_reset(ekf_t h, int f) {
     h->held[k] = 0;
   }
   const size_t sb = h->sig_stride * h->w;
-  char* sig0 = static_cast<char*>(h->sig[0]) + f0 * sb;
-  HIPCHK(hipMemsetAsync(sig0, 0, sb * nf, h->stream));
-  HIPCHK(hipMemsetAsync(h->x[0] + f0 * h->x_stride, 0, h->x_stride * nf * sizeof(double),
-                        h->stream));
-  HIPCHK(hipMemsetAsync(h->ctl + f0, 0, sizeof(FilterCtl) * nf, h->stream));
-  if (h->trace)  // the filters' pose traces restart at record 0
-    HIPCHK(hipMemsetAsync(h->trace_n + f0, 0, sizeof(long long) * nf, h->stream));
+  char* sig0 = static_cast<char*>(h->sig[0].get()) + f0 * sb;
+  HIPCHK(hipMemsetAsync(sig0, 0, sb * nf, h->stream.get()));
+  HIPCHK(hipMemsetAsync(h->x[0].get() + f0 * h->x_stride, 0, h->x_stride * nf * sizeof(double),
+                        h->stream.get()));
+  HIPCHK(hipMemsetAsync(h->ctl.get() + f0, 0, sizeof(FilterCtl) * nf, h->stream.get()));
+  if (h->trace.get())  // the filters' pose traces restart at record 0
+    HIPCHK(hipMemsetAsync(h->trace_n.get() + f0, 0, sizeof(long long) * nf, h->stream.get()));
   if (init_diag(h, sig0, nf)) return EKF_E_HIP;
   return drain(h);
 }
@@ -662,70 +574,55 @@ int ekf_trace_enable(ekf_t h, int capacity) {
   if (!h || capacity < 0) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;  // nothing in flight reads the buffers replaced below
   hipSetDevice(h->cfg.device);
-  TraceRec* recs = nullptr;
-  long long* counts = nullptr;
+  // the new buffers first, so that a failure changes nothing (ekf.h); the old ones go with the move
+  DeviceBuf<TraceRec> recs;
+  DeviceBuf<long long> counts;
   if (capacity > 0) {
     const size_t F = static_cast<size_t>(h->F);
-    // (a failed allocation must not stay behind as the runtime's last error: the launchers
-    // return hipGetLastError())
-    if (hipMalloc(&recs, F * capacity * sizeof(TraceRec)) != hipSuccess) {
-      (void)hipGetLastError();
-      return EKF_E_NOMEM;
-    }
-    if (hipMalloc(&counts, F * sizeof(long long)) != hipSuccess) {
-      (void)hipGetLastError();
-      hipFree(recs);
-      return EKF_E_NOMEM;
-    }
-    if (hipMemset(counts, 0, F * sizeof(long long)) != hipSuccess) {
-      hipFree(recs);
-      hipFree(counts);
-      return EKF_E_HIP;
-    }
+    if (recs.reserve(F * capacity) || counts.reserve(F)) return EKF_E_NOMEM;
+    HIPCHK(hipMemset(counts.get(), 0, F * sizeof(long long)));
   }
-  if (h->trace) hipFree(h->trace);
-  if (h->trace_n) hipFree(h->trace_n);
-  h->trace = recs;
-  h->trace_n = counts;
+  h->trace = std::move(recs);
+  h->trace_n = std::move(counts);
   h->trace_cap = capacity;
   return EKF_OK;
 }
 
 int ekf_trace_count(ekf_t h, int f, long long* appended) {
-  if (!valid(h, f) || !appended || !h->trace) return EKF_E_ARG;
+  if (!valid(h, f) || !appended || !h->trace.get()) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;
-  HIPCHK(hipMemcpy(appended, h->trace_n + f, sizeof(long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(appended, h->trace_n.get() + f, sizeof(long long), hipMemcpyDeviceToHost));
   return EKF_OK;
 }
 
 int ekf_trace_read(ekf_t h, int f, long long first, int n, ekf_trace_rec* out, int* got) {
-  if (!valid(h, f) || !out || !got || !h->trace || first < 0 || n < 0) return EKF_E_ARG;
+  if (!valid(h, f) || !out || !got || !h->trace.get() || first < 0 || n < 0) return EKF_E_ARG;
   *got = 0;
   if (int rc = settle(h)) return rc;
   long long appended = 0;
-  HIPCHK(hipMemcpy(&appended, h->trace_n + f, sizeof(long long), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&appended, h->trace_n.get() + f, sizeof(long long), hipMemcpyDeviceToHost));
   const long long kept = std::min<long long>(appended, h->trace_cap);
   if (first >= kept || n == 0) return EKF_OK;
   const long long k = std::min<long long>(n, kept - first);
-  HIPCHK(hipMemcpy(out, h->trace + static_cast<size_t>(f) * h->trace_cap + first,
+  HIPCHK(hipMemcpy(out, h->trace.get() + static_cast<size_t>(f) * h->trace_cap + first,
                    static_cast<size_t>(k) * sizeof(TraceRec), hipMemcpyDeviceToHost));
   *got = static_cast<int>(k);
   return EKF_OK;
 }
 
 int ekf_trace_clear(ekf_t h, int f) {
-  if (!h || f >= h->F || !h->trace) return EKF_E_ARG;
+  if (!h || f >= h->F || !h->trace.get()) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;
   hipSetDevice(h->cfg.device);
   const int f0 = f < 0 ? 0 : f, nf = f < 0 ? h->F : 1;
-  HIPCHK(hipMemsetAsync(h->trace_n + f0, 0, sizeof(long long) * nf, h->stream));
+  HIPCHK(hipMemsetAsync(h->trace_n.get() + f0, 0, sizeof(long long) * nf, h->stream.get()));
   return drain(h);  // (the bulk stream's next launch is not ordered after the main stream's memset)
 }
 
 int ekf_get_pose(ekf_t h, int f, double* p) {
   if (!valid(h, f) || !p) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;
-  HIPCHK(hipMemcpy(p, h->x[h->plan.parity(f)] + f * h->x_stride, 3 * sizeof(double),
+  HIPCHK(hipMemcpy(p, h->x[h->plan.parity(f)].get() + f * h->x_stride, 3 * sizeof(double),
                    hipMemcpyDeviceToHost));
   return EKF_OK;
 }
@@ -733,7 +630,7 @@ int ekf_get_pose(ekf_t h, int f, double* p) {
 int ekf_get_map_odom(ekf_t h, int f, double* p) {
   if (!valid(h, f) || !p) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;
-  HIPCHK(hipMemcpy(p, h->ctl[f].tmo, 3 * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(p, h->ctl.get()[f].tmo, 3 * sizeof(double), hipMemcpyDeviceToHost));
   return EKF_OK;
 }
 
@@ -742,11 +639,11 @@ int ekf_get_state(ekf_t h, int f, double* state, double* sigma, unsigned* counte
   if (int rc = settle(h)) return rc;
   const int p = h->plan.parity(f);
   if (state)
-    HIPCHK(hipMemcpy(state, h->x[p] + f * h->x_stride, h->n * sizeof(double),
+    HIPCHK(hipMemcpy(state, h->x[p].get() + f * h->x_stride, h->n * sizeof(double),
                      hipMemcpyDeviceToHost));
   if (sigma) {
     std::vector<char> buf(h->sig_stride * h->w);
-    const char* src = static_cast<const char*>(h->sig[p]) + f * h->sig_stride * h->w;
+    const char* src = static_cast<const char*>(h->sig[p].get()) + f * h->sig_stride * h->w;
     HIPCHK(hipMemcpy(buf.data(), src, buf.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < h->n; ++i)
       for (int j = 0; j < h->n; ++j) {
@@ -756,7 +653,8 @@ int ekf_get_state(ekf_t h, int f, double* state, double* sigma, unsigned* counte
                       : reinterpret_cast<const double*>(buf.data())[e];
       }
   }
-  if (counter) HIPCHK(hipMemcpy(counter, &h->ctl[f].counter, sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (counter)
+    HIPCHK(hipMemcpy(counter, &h->ctl.get()[f].counter, sizeof(unsigned), hipMemcpyDeviceToHost));
   return EKF_OK;
 }
 
@@ -767,7 +665,7 @@ int ekf_set_state(ekf_t h, int f, const double* state, const double* sigma, cons
   h->plan.forget(f);
   const int p = h->plan.parity(f);
   if (state)
-    HIPCHK(hipMemcpy(h->x[p] + f * h->x_stride, state, h->n * sizeof(double),
+    HIPCHK(hipMemcpy(h->x[p].get() + f * h->x_stride, state, h->n * sizeof(double),
                      hipMemcpyHostToDevice));
   if (sigma) {
     std::vector<char> buf(h->sig_stride * h->w, 0);
@@ -784,11 +682,11 @@ int ekf_set_state(ekf_t h, int f, const double* state, const double* sigma, cons
         else
           reinterpret_cast<double*>(buf.data())[e] = v;
       }
-    char* dst = static_cast<char*>(h->sig[p]) + f * h->sig_stride * h->w;
+    char* dst = static_cast<char*>(h->sig[p].get()) + f * h->sig_stride * h->w;
     HIPCHK(hipMemcpy(dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
   }
-  if (tmo) HIPCHK(hipMemcpy(h->ctl[f].tmo, tmo, 3 * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(&h->ctl[f].counter, &counter, sizeof(unsigned), hipMemcpyHostToDevice));
+  if (tmo) HIPCHK(hipMemcpy(h->ctl.get()[f].tmo, tmo, 3 * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(&h->ctl.get()[f].counter, &counter, sizeof(unsigned), hipMemcpyHostToDevice));
   h->plan.set_pending(f, false);
   return EKF_OK;
 }
@@ -796,9 +694,9 @@ int ekf_set_state(ekf_t h, int f, const double* state, const double* sigma, cons
 int ekf_get_status(ekf_t h, int f, unsigned* flags) {
   if (!valid(h, f) || !flags) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;
-  HIPCHK(hipMemcpy(flags, &h->ctl[f].status, sizeof(unsigned), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(flags, &h->ctl.get()[f].status, sizeof(unsigned), hipMemcpyDeviceToHost));
   const unsigned z = 0;
-  HIPCHK(hipMemcpy(&h->ctl[f].status, &z, sizeof(unsigned), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(&h->ctl.get()[f].status, &z, sizeof(unsigned), hipMemcpyHostToDevice));
   *flags |= h->held[f];
   h->held[f] = 0;
   return EKF_OK;
@@ -813,43 +711,47 @@ int ekf_get_marginals(ekf_t h, int f, double* pose, double* pose_cov, ekf_lm_mar
   hipSetDevice(h->cfg.device);
   const int f0 = f < 0 ? 0 : f;
   const size_t nf = f < 0 ? h->F : 1, N = h->cfg.n_landmarks;
-  const size_t par_b = up16(h->F * sizeof(int)), pose_b = up16(nf * 3 * sizeof(double)),
-               cov_b = up16(nf * 9 * sizeof(double)), cnt_b = up16(nf * sizeof(unsigned)),
-               lm_b = lm ? nf * N * sizeof(LmMarginal) : 0;
-  if (int rc = eval_reserve(h, par_b + pose_b + cov_b + cnt_b + lm_b)) return rc;
-  char* base = static_cast<char*>(h->eval_buf);
+  int* par = nullptr;
   MarginalOut o{};
-  o.pose = reinterpret_cast<double*>(base + par_b);
-  o.pose_cov = reinterpret_cast<double*>(base + par_b + pose_b);
-  o.counter = reinterpret_cast<unsigned*>(base + par_b + pose_b + cov_b);
-  o.lm = lm ? reinterpret_cast<LmMarginal*>(base + par_b + pose_b + cov_b + cnt_b) : nullptr;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    par = c.take<int>(h->F);
+    o.pose = c.take<double>(nf * 3);
+    o.pose_cov = c.take<double>(nf * 9);
+    o.counter = c.take<unsigned>(nf);
+    o.lm = lm ? c.take<LmMarginal>(nf * N) : nullptr;
+    return c.off;
+  };
+  if (int rc = h->eval_buf.reserve(carve(nullptr))) return rc;
+  carve(h->eval_buf.get());
   EvalArgs a;
-  if (int rc = eval_args(h, reinterpret_cast<int*>(base), f0, &a)) return rc;
+  if (int rc = eval_args(h, par, f0, &a)) return rc;
   HIPCHK(by_dtype(h, [&](auto tag) {
-    return launch_marginals<decltype(tag)>(a, o, static_cast<int>(nf), h->stream);
+    return launch_marginals<decltype(tag)>(a, o, static_cast<int>(nf), h->stream.get());
   }));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream.get()));
   if (pose) HIPCHK(hipMemcpy(pose, o.pose, nf * 3 * sizeof(double), hipMemcpyDeviceToHost));
   if (pose_cov)
     HIPCHK(hipMemcpy(pose_cov, o.pose_cov, nf * 9 * sizeof(double), hipMemcpyDeviceToHost));
   if (counter)
     HIPCHK(hipMemcpy(counter, o.counter, nf * sizeof(unsigned), hipMemcpyDeviceToHost));
-  if (lm) HIPCHK(hipMemcpy(lm, o.lm, lm_b, hipMemcpyDeviceToHost));
+  if (lm) HIPCHK(hipMemcpy(lm, o.lm, nf * N * sizeof(LmMarginal), hipMemcpyDeviceToHost));
   return EKF_OK;
 }
 
 int ekf_eval(ekf_t h, const double* truth_pose, const double* truth_lm, int n_map,
              const double* frame, ekf_eval_rec* out) {
   if (!eval_args_ok(h, truth_pose, truth_lm, n_map, out)) return EKF_E_ARG;
-  return eval_run(h, truth_pose, truth_lm, nullptr, 0, nullptr, n_map, frame, out);
+  return eval_run(h, {truth_pose, truth_lm, nullptr, 0, nullptr, n_map, frame}, false, 0.0, out,
+                  nullptr, nullptr);
 }
 
 int ekf_eval_match(ekf_t h, const double* truth_pose, const double* truth_lm, int n_map,
                    const double* frame, double max_dist, ekf_eval_rec* out,
                    ekf_match_rec* match_out, int* match) {
   if (!match_args_ok(h, truth_pose, truth_lm, n_map, max_dist, out)) return EKF_E_ARG;
-  return eval_match_run(h, truth_pose, truth_lm, nullptr, 0, nullptr, n_map, frame, max_dist, out,
-                        match_out, match);
+  return eval_run(h, {truth_pose, truth_lm, nullptr, 0, nullptr, n_map, frame}, true, max_dist,
+                  out, match_out, match);
 }
 
 int ekf_eval_summary(const ekf_eval_rec* recs, int nf, ekf_eval_sum* out) {
@@ -894,10 +796,11 @@ int ekf_profile_read(ekf_t h, int kind, long long* launches, double* total_ms) {
   auto& pe = h->pe[kind];
   for (size_t i = 0; i < pe.start.size(); ++i) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, pe.start[i], pe.stop[i]) == hipSuccess) h->prof_ms[kind] += ms;
+    if (hipEventElapsedTime(&ms, pe.start[i].get(), pe.stop[i].get()) == hipSuccess)
+      h->prof_ms[kind] += ms;
     h->prof_launches[kind] += 1;
-    h->pool.push_back(pe.start[i]);
-    h->pool.push_back(pe.stop[i]);
+    h->pool.push_back(std::move(pe.start[i]));
+    h->pool.push_back(std::move(pe.stop[i]));
   }
   pe.start.clear();
   pe.stop.clear();

@@ -1,10 +1,12 @@
 // The handle behind include/ekf.h: device memory, the two HIP streams and what orders them, the
-// upload ring, profiling, and the host planner. Shared by the scheduler (ekf_sched.cpp) and the C
-// ABI (ekf_api.cpp), which also declares here what it calls of the scheduler.
+// upload ring, profiling, and the host planner. The HIP resources are owning members
+// (hip_owned.hpp), so deleting the handle releases them. Shared by the scheduler (ekf_sched.cpp)
+// and the C ABI (ekf_api.cpp), which also declares here what it calls of the scheduler.
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <utility>
 #include <vector>
 
 #include "ekf.h"
@@ -12,20 +14,20 @@
 #include "ekf_launch.hpp"
 #include "ekf_plan.hpp"
 #include "eval_math.hpp"
+#include "hip_owned.hpp"
 
 namespace ekfslam {
 
 constexpr int kRing = 16;  // pinned staging slots (host may run this many uploads ahead)
 
 struct StageSlot {
-  MsgDesc* p = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;
+  PinnedBuf<MsgDesc> p;
+  Event ev{hipEventDisableTiming};  // the slot's last upload is done
   bool used = false;
 };
 
 struct ProfEvents {
-  std::vector<hipEvent_t> start, stop;
+  std::vector<Event> start, stop;
 };
 
 // What timed() brackets with events; the numerals are ekf_profile_read's `kind` (ABI).
@@ -65,8 +67,10 @@ struct ekf_ctx {
   ekf_config cfg{};
   int n = 0, ld = 0, ldk = 0, F = 0;
   size_t w = 8;
-  hipStream_t stream = nullptr;  // chain + factors (+ association, posterior)
-  hipStream_t bulk = nullptr;    // Σ passes: chunk t's pass overlaps chunk t+1's chain
+  // Members are destroyed in reverse order of declaration: the streams come first, so they outlive
+  // every buffer and event used on them (ekf_destroy synchronises both before deleting the handle).
+  ekfslam::Stream stream;  // chain + factors (+ association, posterior)
+  ekfslam::Stream bulk;    // Σ passes: chunk t's pass overlaps chunk t+1's chain
   bool serial = false;           // EKF_SERIAL=1: every kernel on one stream (per-dispatch PMC)
   bool resident = false;         // n ≤ kResidentMaxN, fp64: Σ in registers (ekf_resident.hip)
   bool defer = false;            // ekf_defer: plan now, upload and launch later
@@ -81,42 +85,46 @@ struct ekf_ctx {
                                  // on the bulk stream must wait for it before rewriting ddesc
   bool epoch_owed = false;       // the last Σ pass published no device epoch (the flush's last
                                  // launch: the next flush joins the bulk stream on the host)
-  ekfslam::AmArgs am{};          // k_assoc_msg scratch (allocated at the first association chunk)
+  ekfslam::AmArgs am{};          // k_assoc_msg scratch (allocated at the first association chunk),
+  ekfslam::DeviceBuf<ekfslam::AmHist> am_hist;  // ... which these own
+  ekfslam::DeviceBuf<ekfslam::AmCur> am_cur;
+  ekfslam::DeviceBuf<unsigned long long> am_gran;
   int am_route = 0;              // unknown association: EKF_ASSOC_* (fixed at ekf_create)
   int am_route_j = 0;            // ... for the Joseph-form kernel (its larger LDS may fit fewer)
   int am_group = 1;              // filters per k_assoc_msg launch (co-resident, assoc_msg_group)
   int am_group_j = 1;            // ... Joseph form
   int bulk_cus_per_xcd = 0;      // CUs the bulk stream may use on each XCD
   int main_cus_per_xcd = 0;      // CUs the main stream may use on each XCD (0: every CU, no mask)
-  unsigned* fatal_h = nullptr;   // host-mapped: a device poll timed out (EKF_E_TIMEOUT)
+  // host-mapped: a device poll timed out (EKF_E_TIMEOUT)
+  ekfslam::PinnedBuf<unsigned> fatal_h{hipHostMallocMapped | hipHostMallocCoherent};
   unsigned* fatal_d = nullptr;   // its device address (PassArgs::fatal)
-  hipEvent_t ev_chain = nullptr;          // main → bulk: the chunk's chain is done
-  hipEvent_t ev_join = nullptr;           // bulk → main: everything issued so far
+  ekfslam::Event ev_chain{hipEventDisableTiming};  // main → bulk: the chunk's chain is done
+  ekfslam::Event ev_join{hipEventDisableTiming};   // bulk → main: everything issued so far
   bool devsync = false;                   // streams synchronise through device epochs
-  unsigned* sync = nullptr;               // device epochs: Σ pass done, its ticket, chains done
-  hipEvent_t ev_sig[2] = {nullptr, nullptr};  // bulk → main: Σ pass of launch s, by s & 1
+  ekfslam::DeviceBuf<unsigned> sync;      // device epochs: Σ pass done, its ticket, chains done
+  // bulk → main: Σ pass of launch s, by s & 1
+  ekfslam::Event ev_sig[2] = {ekfslam::Event{hipEventDisableTiming},
+                              ekfslam::Event{hipEventDisableTiming}};
   long long seq = 0;                      // launch pairs issued
-  void* sig[2] = {nullptr, nullptr};
-  double* x[2] = {nullptr, nullptr};
-  void* kcat = nullptr;
-  void* mcat = nullptr;
-  ekfslam::FilterCtl* ctl = nullptr;
-  ekfslam::ChunkRec* rec = nullptr;
-  void* stage = nullptr; // StageRec<T>[2][F]: a kLook chain's rebuild operands (kStageIn)
-  ekfslam::MsgDesc* ddesc = nullptr;
+  ekfslam::DeviceBuf<void> sig[2];        // (void: fp32 or fp64 by cfg.dtype, sized in bytes)
+  ekfslam::DeviceBuf<double> x[2];
+  ekfslam::DeviceBuf<void> kcat, mcat;
+  ekfslam::DeviceBuf<ekfslam::FilterCtl> ctl;
+  ekfslam::DeviceBuf<ekfslam::ChunkRec> rec;
+  ekfslam::DeviceBuf<void> stage;  // StageRec<T>[2][F]: a kLook chain's rebuild operands (kStageIn)
+  ekfslam::DeviceBuf<ekfslam::MsgDesc> ddesc;
   // pose trace (ekf_trace_enable; off: all null / 0, and every launch's PassArgs says so)
-  ekfslam::TraceRec* trace = nullptr;  // [F][trace_cap]
-  long long* trace_n = nullptr;        // [F] records appended
-  int trace_cap = 0;
+  ekfslam::DeviceBuf<ekfslam::TraceRec> trace;  // [F][trace_cap]
+  ekfslam::DeviceBuf<long long> trace_n;        // [F] records appended
+  int trace_cap = 0;  // (not the buffer's capacity / F alone: the kernels' argument)
   // ekf_get_marginals / ekf_eval: one device buffer for a call's inputs and outputs (grown, never
   // shrunk; freed with the handle)
-  void* eval_buf = nullptr;
-  size_t eval_cap = 0;
+  ekfslam::DeviceBuf<char> eval_buf;
   size_t sig_stride = 0, x_stride = 0, km_stride = 0;
   // ekf_replay_device: the planning state lives on the device while dev_plan (ping-pong by
   // dstate_cur); the planner adopts it (adopt_device_plan) before it is used again
-  ekfslam::PlanState* dstate[2] = {nullptr, nullptr};
-  ekfslam::PlanState* hstate = nullptr;  // pinned: host → device and back
+  ekfslam::DeviceBuf<ekfslam::PlanState> dstate[2];
+  ekfslam::PinnedBuf<ekfslam::PlanState> hstate;  // pinned: host → device and back
   int dstate_cur = 0;
   bool dev_plan = false;
   hipStream_t plan_stream = nullptr;  // the stream the last device planner ran on
@@ -124,26 +132,24 @@ struct ekf_ctx {
   unsigned need_plan = 0;     // the next chain launch polls kSyncPlan for this (0: none)
   // lm_replay_into: the messages' odometry, staged in pinned memory (ev_odom: its last upload is
   // done, the staging may be rewritten) and uploaded on the planning stream
-  double* odom_d = nullptr;
-  double* odom_h = nullptr;
-  size_t odom_cap = 0;  // doubles either holds
-  hipEvent_t ev_odom = nullptr;
+  ekfslam::DeviceBuf<double> odom_d;
+  ekfslam::PinnedBuf<double> odom_h;  // (the same capacity, in doubles)
+  ekfslam::Event ev_odom{hipEventDisableTiming};  // created at the first staging
   // the host mirror and the launch plan (ekf_set_joseph's form lives there too)
   ekfslam::Planner plan;
   std::vector<unsigned> held;    // status bits taken off the device word by the synchronous forms
                                  // (take_numeric); ekf_get_status reports and clears them too
-  size_t ddesc_cap = 0;
-  // pinned staging ring (the host may run kRing uploads ahead of the device), every slot ring_cap
+  // pinned staging ring (the host may run kRing uploads ahead of the device), every slot the same
+  // capacity
   ekfslam::StageSlot ring[ekfslam::kRing];
-  size_t ring_cap = 0;
   int ring_next = 0;
   // profiling
   bool prof = false;
   ekfslam::ProfEvents pe[ekfslam::kProfSlots];
-  std::vector<hipEvent_t> pool;
-  long long prof_launches[ekfslam::kProfSlots] = {0, 0, 0, 0, 0};
+  std::vector<ekfslam::Event> pool;  // timing events ekf_profile_read has read, for timed()
+  long long prof_launches[ekfslam::kProfSlots] = {};
   long long prof_chunks = 0;  // chunks the timed chain launches walked
-  double prof_ms[ekfslam::kProfSlots] = {0, 0, 0, 0, 0};
+  double prof_ms[ekfslam::kProfSlots] = {};
 };
 
 #define HIPCHK(expr)                       \
@@ -157,6 +163,30 @@ namespace ekfslam {
 template <typename Fn>
 auto by_dtype(const ekf_ctx* h, Fn fn) {
   return h->cfg.dtype == EKF_F32 ? fn(float{}) : fn(double{});
+}
+
+// Launch `fn(start, stop)` bracketed by two pooled timing events when profiling (ekf_profile_read
+// returns them to the pool); fn(nullptr, nullptr) when not, or when the pool cannot be brought to
+// two events: one event alone stays pooled.
+template <typename Fn>
+int timed(ekf_ctx* h, ProfSlot kind, Fn fn) {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  auto& pool = h->pool;
+  while (h->prof && pool.size() < 2) {
+    pool.emplace_back();
+    if (pool.back().create() == EKF_OK) continue;
+    pool.pop_back();
+    break;
+  }
+  if (h->prof && pool.size() >= 2) {
+    for (auto* v : {&h->pe[kind].start, &h->pe[kind].stop}) {
+      v->push_back(std::move(pool.back()));
+      pool.pop_back();
+    }
+    e0 = h->pe[kind].start.back().get();
+    e1 = h->pe[kind].stop.back().get();
+  }
+  return fn(e0, e1) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 // ---- ekf_sched.cpp ----

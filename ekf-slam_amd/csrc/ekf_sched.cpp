@@ -17,21 +17,21 @@ namespace {
 template <typename T>
 PassArgs<T> args(ekf_ctx* h, const MsgDesc* desc, int f0) {
   PassArgs<T> a{};
-  a.sig[0] = static_cast<T*>(h->sig[0]);
-  a.sig[1] = static_cast<T*>(h->sig[1]);
+  a.sig[0] = static_cast<T*>(h->sig[0].get());
+  a.sig[1] = static_cast<T*>(h->sig[1].get());
   a.sig_stride = h->sig_stride;
-  a.x[0] = h->x[0];
-  a.x[1] = h->x[1];
+  a.x[0] = h->x[0].get();
+  a.x[1] = h->x[1].get();
   a.x_stride = h->x_stride;
-  a.kcat = static_cast<T*>(h->kcat);
-  a.mcat = static_cast<T*>(h->mcat);
+  a.kcat = static_cast<T*>(h->kcat.get());
+  a.mcat = static_cast<T*>(h->mcat.get());
   a.km_stride = h->km_stride;
   a.ldk = h->ldk;
-  a.ctl = h->ctl;
-  a.rec = h->rec;
+  a.ctl = h->ctl.get();
+  a.rec = h->rec.get();
   a.rec_stride = static_cast<size_t>(h->F);
-  a.stage = static_cast<StageRec<T>*>(h->stage);
-  a.sync = h->sync;
+  a.stage = static_cast<StageRec<T>*>(h->stage.get());
+  a.sync = h->sync.get();
   a.fatal = h->fatal_d;
   a.desc = desc;
   a.n = h->n;
@@ -43,51 +43,24 @@ PassArgs<T> args(ekf_ctx* h, const MsgDesc* desc, int f0) {
   a.gate = h->cfg.mah_gate;
   a.joseph = h->plan.joseph() ? 1 : 0;
   a.chain_fast = h->chain_fast ? 1 : 0;
-  a.trace = h->trace;
-  a.trace_n = h->trace_n;
+  a.trace = h->trace.get();
+  a.trace_n = h->trace_n.get();
   a.trace_cap = h->trace_cap;
   return a;
 }
 
-hipEvent_t pool_get(ekf_ctx* h) {
-  if (!h->pool.empty()) {
-    hipEvent_t e = h->pool.back();
-    h->pool.pop_back();
-    return e;
-  }
-  hipEvent_t e = nullptr;
-  if (hipEventCreate(&e) != hipSuccess) return nullptr;
-  return e;
-}
-
-// Launch `fn` bracketed by events when profiling.
-template <typename Fn>
-int timed(ekf_ctx* h, ProfSlot kind, Fn fn) {
-  hipEvent_t a = nullptr, b = nullptr;
-  if (h->prof) {
-    a = pool_get(h);
-    b = pool_get(h);
-  }
-  const hipError_t e = fn(a && b ? a : nullptr, a && b ? b : nullptr);
-  if (h->prof && a && b) {
-    h->pe[kind].start.push_back(a);
-    h->pe[kind].stop.push_back(b);
-  }
-  return e == hipSuccess ? EKF_OK : EKF_E_HIP;
-}
-
 // Main waits for everything issued to the bulk stream so far.
 int join_bulk(ekf_ctx* h) {
-  if (hipEventRecord(h->ev_join, h->bulk) != hipSuccess ||
-      hipStreamWaitEvent(h->stream, h->ev_join, 0) != hipSuccess)
+  if (hipEventRecord(h->ev_join.get(), h->bulk.get()) != hipSuccess ||
+      hipStreamWaitEvent(h->stream.get(), h->ev_join.get(), 0) != hipSuccess)
     return EKF_E_HIP;
   return EKF_OK;
 }
 
 // Bulk waits for everything issued to the main stream so far.
 int fork_bulk(ekf_ctx* h) {
-  HIPCHK(hipEventRecord(h->ev_chain, h->stream));
-  HIPCHK(hipStreamWaitEvent(h->bulk, h->ev_chain, 0));
+  HIPCHK(hipEventRecord(h->ev_chain.get(), h->stream.get()));
+  HIPCHK(hipStreamWaitEvent(h->bulk.get(), h->ev_chain.get(), 0));
   return EKF_OK;
 }
 
@@ -124,7 +97,7 @@ int launch_group(ekf_ctx* h, const MsgDesc* dptr, const Launch* L, int f0, int n
   const unsigned s0 = static_cast<unsigned>(h->seq);
   a.seq = s0;
   const bool two = pipelined && !h->serial;
-  hipStream_t ms = h->stream, bs = two ? h->bulk : h->stream;
+  hipStream_t ms = h->stream.get(), bs = two ? h->bulk.get() : h->stream.get();
   a.polls = two && h->devsync ? 1 : 0;
   a.need_plan = a.polls ? h->need_plan : 0u;
   h->need_plan = 0;
@@ -138,7 +111,7 @@ int launch_group(ekf_ctx* h, const MsgDesc* dptr, const Launch* L, int f0, int n
   }
   if (pipelined && !nolook) {
     // events: a rebuilding (kLook) chain needs the Σ pass two launches back
-    if (!h->devsync) HIPCHK(hipStreamWaitEvent(ms, h->ev_sig[s0 & 1], 0));
+    if (!h->devsync) HIPCHK(hipStreamWaitEvent(ms, h->ev_sig[s0 & 1].get(), 0));
   } else if (!a.polls) {
     // a chain that gathers its own Σ_in needs the previous pass: everything on the bulk stream
     if (join_bulk(h)) return EKF_E_HIP;
@@ -172,7 +145,7 @@ int launch_group(ekf_ctx* h, const MsgDesc* dptr, const Launch* L, int f0, int n
       return launch_sigma_pass<T>(ai, nf, last ? publish_end : !in_group, stage, bs, e0, e1);
     });
     if (rc) return rc;
-    if (!h->devsync) HIPCHK(hipEventRecord(h->ev_sig[(s0 + i) & 1], bs));
+    if (!h->devsync) HIPCHK(hipEventRecord(h->ev_sig[(s0 + i) & 1].get(), bs));
   }
   h->seq += nchunks;
   h->epoch_owed = a.polls && !publish_end;
@@ -216,7 +189,7 @@ int assoc(ekf_ctx* h, const MsgDesc* dptr, int f0, int nf, bool poll) {
     a.polls = poll ? 1 : 0;
     a.need_sigma = poll ? static_cast<unsigned>(h->seq) : 0u;
     return timed(h, kProfAssoc, [&](hipEvent_t e0, hipEvent_t e1) {
-      return launch_assoc<T>(a, nf, h->stream, e0, e1);
+      return launch_assoc<T>(a, nf, h->stream.get(), e0, e1);
     });
   });
 }
@@ -233,7 +206,7 @@ int assoc_cus_per_xcd(const ekf_ctx* h) {
 
 // k_assoc_msg's tables and granules for every filter (once; zeroed so no stale tag matches)
 int ensure_am(ekf_ctx* h) {
-  if (h->am.hist) return EKF_OK;
+  if (h->am.hist) return EKF_OK;  // (set below, once all three buffers and the memset succeeded)
   const int G = (h->cfg.n_landmarks + kAmSlots - 1) / kAmSlots;
   const size_t Np = static_cast<size_t>(G) * kAmSlots, F = static_cast<size_t>(h->F);
   AmArgs b{};
@@ -246,21 +219,13 @@ int ensure_am(ekf_ctx* h) {
   b.spin = 1u << 22;  // ≈ 0.1 s of polls per exchange
   if (const char* e = std::getenv("EKF_AM_SPIN_LOG2")) b.spin = 1u << std::min(std::atoi(e), 30);
   if (const char* e = std::getenv("EKF_AM_DROP")) b.drop = std::atoi(e) != 0 ? 1 : 0;
-  auto release = [&]() {
-    if (b.hist) hipFree(b.hist);
-    if (b.cur) hipFree(b.cur);
-    if (b.gran) hipFree(b.gran);
-  };
-  if (hipMalloc(&b.hist, sizeof(AmHist) * b.hist_stride * F) != hipSuccess ||
-      hipMalloc(&b.cur, sizeof(AmCur) * b.cur_stride * F) != hipSuccess ||
-      hipMalloc(&b.gran, sizeof(unsigned long long) * b.gran_stride * F) != hipSuccess) {
-    release();
-    return EKF_E_NOMEM;
-  }
-  if (hipMemset(b.gran, 0, sizeof(unsigned long long) * b.gran_stride * F) != hipSuccess) {
-    release();
-    return EKF_E_HIP;
-  }
+  if (h->am_hist.reserve(b.hist_stride * F) || h->am_cur.reserve(b.cur_stride * F) ||
+      h->am_gran.reserve(b.gran_stride * F))
+    return reset_all(h->am_hist, h->am_cur, h->am_gran);
+  b.hist = h->am_hist.get();
+  b.cur = h->am_cur.get();
+  b.gran = h->am_gran.get();
+  HIPCHK(hipMemset(b.gran, 0, sizeof(unsigned long long) * b.gran_stride * F));
   h->am = b;
   for (int jv = 0; jv < 2; ++jv) {
     const int slots_x =
@@ -276,7 +241,7 @@ int ensure_am(ekf_ctx* h) {
 // the main stream first if the latter ran anything since (a chain wrote t_map_odom there).
 int assoc_msg_group(ekf_ctx* h, const MsgDesc* dptr, int f0, int nf, bool publish_end) {
   if (int rc = ensure_am(h)) return rc;
-  hipStream_t bs = h->serial ? h->stream : h->bulk;
+  hipStream_t bs = h->serial ? h->stream.get() : h->bulk.get();
   if (!h->serial && h->main_dirty && fork_bulk_clean(h)) return EKF_E_HIP;
   const unsigned seq = static_cast<unsigned>(h->seq);
   // A filter's G workgroups spin on each other, so a launch holds only as many filters as the
@@ -305,7 +270,7 @@ int assoc_msg_group(ekf_ctx* h, const MsgDesc* dptr, int f0, int nf, bool publis
     });
   });
   if (rc) return rc;
-  if (!h->devsync) HIPCHK(hipEventRecord(h->ev_sig[seq & 1], bs));
+  if (!h->devsync) HIPCHK(hipEventRecord(h->ev_sig[seq & 1].get(), bs));
   h->seq += 1;
   h->epoch_owed = h->devsync && !h->serial && !publish_end;
   return EKF_OK;
@@ -314,7 +279,7 @@ int assoc_msg_group(ekf_ctx* h, const MsgDesc* dptr, int f0, int nf, bool publis
 int posterior_launch(ekf_ctx* h, const MsgDesc* dp, int f0, int nf) {
   const hipError_t e = by_dtype(h, [&](auto tag) {
     using T = decltype(tag);
-    return launch_posterior<T>(args<T>(h, dp, f0), nf, h->stream);
+    return launch_posterior<T>(args<T>(h, dp, f0), nf, h->stream.get());
   });
   return e == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
@@ -323,25 +288,20 @@ int posterior_launch(ekf_ctx* h, const MsgDesc* dp, int f0, int nf) {
 // drains both streams). The pinned ring — host-planned uploads only, so ekf_replay_device never
 // grows it — grows EVERY slot together, so an allocation happens the first time a plan this large
 // is seen, never on a later same-sized call that lands on a ring slot not used before (a
-// hipHostMalloc costs ≈ 120 µs, a device re-allocation a drain: round 3 measured both inside a
+// pinned allocation costs ≈ 120 µs, a device re-allocation a drain: round 3 measured both inside a
 // 20-message bench region). Host plans are flushed every kFlushDesc descriptors (plus one
 // message), which bounds the ring.
 int reserve_device(ekf_ctx* h, size_t need) {
-  if (need <= h->ddesc_cap) return EKF_OK;
+  if (need <= h->ddesc.capacity()) return EKF_OK;
   if (drain(h)) return EKF_E_HIP;  // the previous launch may still read the old buffer
-  if (h->ddesc) HIPCHK(hipFree(h->ddesc));
-  h->ddesc = nullptr;
-  const size_t cap = std::max(need, 2 * h->ddesc_cap);
-  if (hipMalloc(&h->ddesc, cap * sizeof(MsgDesc)) != hipSuccess) return EKF_E_NOMEM;
-  h->ddesc_cap = cap;
-  return EKF_OK;
+  return h->ddesc.reserve(need, 2 * h->ddesc.capacity());
 }
 
 // The next pinned staging slot, once the device is done with its last upload.
 int next_slot(ekf_ctx* h, StageSlot** out) {
   StageSlot& sl = h->ring[h->ring_next];
   h->ring_next = (h->ring_next + 1) % kRing;
-  if (sl.used) HIPCHK(hipEventSynchronize(sl.ev));
+  if (sl.used) HIPCHK(hipEventSynchronize(sl.ev.get()));
   *out = &sl;
   return EKF_OK;
 }
@@ -359,8 +319,8 @@ int flush_resident(ekf_ctx* h) {
   StageSlot* slp = nullptr;
   if (int rc = next_slot(h, &slp)) return rc;
   StageSlot& sl = *slp;
-  std::memcpy(sl.p, pd.data(), nd * sizeof(MsgDesc));
-  PlanEntry* pe = reinterpret_cast<PlanEntry*>(sl.p + nd);
+  std::memcpy(sl.p.get(), pd.data(), nd * sizeof(MsgDesc));
+  PlanEntry* pe = reinterpret_cast<PlanEntry*>(sl.p.get() + nd);
   int flo = INT_MAX, fhi = 0;
   for (size_t i = 0; i < nl; ++i) {
     const Launch& L = pl[i];
@@ -368,13 +328,14 @@ int flush_resident(ekf_ctx* h) {
     flo = std::min(flo, L.f0);
     fhi = std::max(fhi, L.f0 + L.nf);
   }
-  HIPCHK(hipMemcpyAsync(h->ddesc, sl.p, ns * sizeof(MsgDesc), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipEventRecord(sl.ev, h->stream));
+  HIPCHK(hipMemcpyAsync(h->ddesc.get(), sl.p.get(), ns * sizeof(MsgDesc), hipMemcpyHostToDevice,
+                        h->stream.get()));
+  HIPCHK(hipEventRecord(sl.ev.get(), h->stream.get()));
   sl.used = true;
-  const PassArgs<double> a = args<double>(h, h->ddesc, 0);
-  const PlanEntry* dplan = reinterpret_cast<const PlanEntry*>(h->ddesc + nd);
+  const PassArgs<double> a = args<double>(h, h->ddesc.get(), 0);
+  const PlanEntry* dplan = reinterpret_cast<const PlanEntry*>(h->ddesc.get() + nd);
   const int rc = timed(h, kProfResident, [&](hipEvent_t e0, hipEvent_t e1) {
-    return launch_resident(a, dplan, static_cast<int>(nl), flo, fhi - flo, h->stream, e0, e1);
+    return launch_resident(a, dplan, static_cast<int>(nl), flo, fhi - flo, h->stream.get(), e0, e1);
   });
   h->plan.clear();
   return rc;
@@ -383,13 +344,10 @@ int flush_resident(ekf_ctx* h) {
 // The device replays' planning state: two device copies (ping-pong by dstate_cur) and the pinned
 // host copy, allocated at the first device replay.
 int ensure_plan_state(ekf_ctx* h) {
-  if (h->dstate[0]) return EKF_OK;
   const size_t F = static_cast<size_t>(h->F);
-  for (PlanState*& p : h->dstate)
-    if (hipMalloc(&p, F * sizeof(PlanState)) != hipSuccess) return EKF_E_NOMEM;
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->hstate), F * sizeof(PlanState),
-                    hipHostMallocDefault) != hipSuccess)
-    return EKF_E_NOMEM;
+  if (h->hstate.capacity() >= F) return EKF_OK;  // (reserved last: all three are there)
+  if (h->dstate[0].reserve(F) || h->dstate[1].reserve(F) || h->hstate.reserve(F))
+    return reset_all(h->dstate[0], h->dstate[1], h->hstate);
   return EKF_OK;
 }
 
@@ -397,8 +355,8 @@ int ensure_plan_state(ekf_ctx* h) {
 // chain on the device.
 int export_plan_state(ekf_ctx* h, hipStream_t ps) {
   if (h->dev_plan) return EKF_OK;
-  h->plan.export_state(h->hstate);
-  HIPCHK(hipMemcpyAsync(h->dstate[h->dstate_cur], h->hstate, h->F * sizeof(PlanState),
+  h->plan.export_state(h->hstate.get());
+  HIPCHK(hipMemcpyAsync(h->dstate[h->dstate_cur].get(), h->hstate.get(), h->F * sizeof(PlanState),
                         hipMemcpyHostToDevice, ps));
   h->dev_plan = true;
   return EKF_OK;
@@ -408,29 +366,24 @@ int export_plan_state(ekf_ctx* h, hipStream_t ps) {
 // handle's pinned staging, once the last upload has left it (stage_odom), then onto the device on
 // the stream that reads it (upload_odom).
 int stage_odom(ekf_ctx* h, const double* host_odom, size_t no) {
-  if (!h->ev_odom) HIPCHK(hipEventCreateWithFlags(&h->ev_odom, hipEventDisableTiming));
-  if (no > h->odom_cap) {
+  if (int rc = h->ev_odom.create()) return rc;
+  if (no > h->odom_h.capacity()) {  // (reserved last: both hold this much)
     if (drain(h)) return EKF_E_HIP;  // a kernel in flight may still read the old buffer
-    if (h->odom_d) HIPCHK(hipFree(h->odom_d));
-    if (h->odom_h) HIPCHK(hipHostFree(h->odom_h));
-    h->odom_d = h->odom_h = nullptr;
-    h->odom_cap = 0;
-    const size_t cap = std::max(no, static_cast<size_t>(3 * 64) * h->F);
-    if (hipMalloc(&h->odom_d, cap * sizeof(double)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&h->odom_h), cap * sizeof(double),
-                      hipHostMallocDefault) != hipSuccess)
-      return EKF_E_NOMEM;
-    h->odom_cap = cap;
+    const size_t floor = static_cast<size_t>(3 * 64) * h->F;
+    reset_all(h->odom_d, h->odom_h);  // (both freed before either is allocated, as ever)
+    if (h->odom_d.reserve(no, floor) || h->odom_h.reserve(no, floor))
+      return reset_all(h->odom_d, h->odom_h);
   } else {
-    HIPCHK(hipEventSynchronize(h->ev_odom));  // the last upload has left the staging
+    HIPCHK(hipEventSynchronize(h->ev_odom.get()));  // the last upload has left the staging
   }
-  std::memcpy(h->odom_h, host_odom, no * sizeof(double));
+  std::memcpy(h->odom_h.get(), host_odom, no * sizeof(double));
   return EKF_OK;
 }
 
 int upload_odom(ekf_ctx* h, size_t no, hipStream_t ps) {
-  HIPCHK(hipMemcpyAsync(h->odom_d, h->odom_h, no * sizeof(double), hipMemcpyHostToDevice, ps));
-  HIPCHK(hipEventRecord(h->ev_odom, ps));
+  HIPCHK(hipMemcpyAsync(h->odom_d.get(), h->odom_h.get(), no * sizeof(double),
+                        hipMemcpyHostToDevice, ps));
+  HIPCHK(hipEventRecord(h->ev_odom.get(), ps));
   return EKF_OK;
 }
 
@@ -462,8 +415,11 @@ int create_streams(ekf_ctx* h) {
     const int words = (cus + 31) / 32;
     std::vector<uint32_t> mmain(words, 0), mbulk(words, 0);
     for (int b = 0; b < cus; ++b) (b < split * kXcd ? mmain : mbulk)[b / 32] |= 1u << (b % 32);
-    if (hipExtStreamCreateWithCUMask(&h->stream, words, mmain.data()) == hipSuccess &&
-        hipExtStreamCreateWithCUMask(&h->bulk, words, mbulk.data()) == hipSuccess) {
+    hipStream_t sm = nullptr, sb = nullptr;
+    const bool main_ok = hipExtStreamCreateWithCUMask(&sm, words, mmain.data()) == hipSuccess;
+    if (main_ok) h->stream.adopt(sm);  // (without its twin, create() below replaces it)
+    if (main_ok && hipExtStreamCreateWithCUMask(&sb, words, mbulk.data()) == hipSuccess) {
+      h->bulk.adopt(sb);
       // device-epoch hand-offs by default; EKF_DEVSYNC=0 synchronises the streams with events
       // (same kernels, one chain launch per chunk: bit-identical to the single-stream order)
       // A persistent multi-chunk chain launch needs every filter's chain resident at once (a
@@ -474,11 +430,8 @@ int create_streams(ekf_ctx* h) {
       h->devsync = !(e && std::atoi(e) == 0) && h->F <= split * kXcd;
       return EKF_OK;
     }
-    if (h->stream) hipStreamDestroy(h->stream);
-    h->stream = nullptr;
   }
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&h->bulk, hipStreamNonBlocking) != hipSuccess)
+  if (h->stream.create(hipStreamNonBlocking) || h->bulk.create(hipStreamNonBlocking))
     return EKF_E_HIP;
   return EKF_OK;
 }
@@ -496,27 +449,25 @@ int am_route(ekf_ctx* h, bool joseph) {
 
 // Both streams idle (before host reads/writes of device state).
 int drain(ekf_ctx* h) {
-  HIPCHK(hipStreamSynchronize(h->bulk));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->bulk.get()));
+  HIPCHK(hipStreamSynchronize(h->stream.get()));
   return EKF_OK;
 }
 
 int reserve_upload(ekf_ctx* h, size_t need) {
   if (int rc = reserve_device(h, need)) return rc;
-  if (need > h->ring_cap || !h->ring[0].p) {
-    const size_t cap = std::max(need, std::min(2 * h->ring_cap, h->ddesc_cap));
-    for (StageSlot& sl : h->ring) {
-      if (sl.used) HIPCHK(hipEventSynchronize(sl.ev));
-      if (sl.p) HIPCHK(hipHostFree(sl.p));
-      sl.p = nullptr;
-      sl.used = false;
-      if (hipHostMalloc(reinterpret_cast<void**>(&sl.p), cap * sizeof(MsgDesc),
-                        hipHostMallocDefault) != hipSuccess)
-        return EKF_E_NOMEM;
-      sl.cap = cap;
-    }
-    h->ring_cap = cap;
+  const size_t ring_cap = h->ring[kRing - 1].p.capacity();  // (reserved last: every slot's)
+  if (need <= ring_cap) return EKF_OK;
+  const size_t floor = std::min(2 * ring_cap, h->ddesc.capacity());
+  for (StageSlot& sl : h->ring) {  // no upload in flight reads a slot that is freed below
+    if (sl.used) HIPCHK(hipEventSynchronize(sl.ev.get()));
+    sl.used = false;
   }
+  for (StageSlot& sl : h->ring)
+    if (sl.p.reserve(need, floor)) {
+      for (StageSlot& o : h->ring) o.p.reset();  // all or nothing: the guard reads one slot
+      return EKF_E_NOMEM;
+    }
   return EKF_OK;
 }
 
@@ -524,7 +475,7 @@ int init_diag(ekf_ctx* h, void* sig0, int nf) {
   const hipError_t e = by_dtype(h, [&](auto tag) {
     using T = decltype(tag);
     return launch_init_diag<T>(static_cast<T*>(sig0), h->sig_stride, h->n, h->ld, h->cfg.init_var,
-                               nf, h->stream);
+                               nf, h->stream.get());
   });
   return e == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
@@ -539,18 +490,19 @@ int flush(ekf_ctx* h) {
   StageSlot* slp = nullptr;
   if (int rc = next_slot(h, &slp)) return rc;
   StageSlot& sl = *slp;
-  std::memcpy(sl.p, h->plan.desc().data(), nd * sizeof(MsgDesc));
+  std::memcpy(sl.p.get(), h->plan.desc().data(), nd * sizeof(MsgDesc));
   if (join_bulk(h)) return EKF_E_HIP;  // the bulk stream may still read descriptors
-  HIPCHK(hipMemcpyAsync(h->ddesc, sl.p, nd * sizeof(MsgDesc), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->ddesc.get(), sl.p.get(), nd * sizeof(MsgDesc), hipMemcpyHostToDevice,
+                        h->stream.get()));
   // the bulk stream reads these descriptors too: one main → bulk hop per upload
   if (fork_bulk_clean(h)) return EKF_E_HIP;
-  HIPCHK(hipEventRecord(sl.ev, h->stream));
+  HIPCHK(hipEventRecord(sl.ev.get(), h->stream.get()));
   sl.used = true;
   int rc = EKF_OK;
   const size_t nl = pl.size();
   for (size_t li = 0; li < nl && !rc;) {
     const Launch& L = pl[li];
-    const MsgDesc* dp = h->ddesc + L.off;
+    const MsgDesc* dp = h->ddesc.get() + L.off;
     if (L.kind == kLaunchKnown) {  // a run of known-association chunks → one persistent chain launch
       size_t lj = li + 1;
       if (h->devsync && !h->serial)  // the bulk kernels must run beside the chain launch
@@ -606,10 +558,10 @@ int submit(ekf_ctx* h) {
 int adopt_device_plan(ekf_ctx* h) {
   if (!h->dev_plan) return EKF_OK;
   hipSetDevice(h->cfg.device);
-  HIPCHK(hipMemcpyAsync(h->hstate, h->dstate[h->dstate_cur], h->F * sizeof(PlanState),
-                        hipMemcpyDeviceToHost, h->plan_stream ? h->plan_stream : h->stream));
+  HIPCHK(hipMemcpyAsync(h->hstate.get(), h->dstate[h->dstate_cur].get(), h->F * sizeof(PlanState),
+                        hipMemcpyDeviceToHost, h->plan_stream ? h->plan_stream : h->stream.get()));
   if (drain(h)) return EKF_E_HIP;
-  h->plan.adopt(h->hstate);
+  h->plan.adopt(h->hstate.get());
   h->dev_plan = false;
   return EKF_OK;
 }
@@ -624,7 +576,7 @@ int settle(ekf_ctx* h) {
 // After a drain: did a device poll of this handle time out since the last report? Reported once
 // (EKF_E_TIMEOUT); which filters it hit stays in their status (EKF_FLAG_TIMEOUT).
 int take_fatal(ekf_ctx* h) {
-  volatile unsigned* p = h->fatal_h;
+  volatile unsigned* p = h->fatal_h.get();
   if (!p || *p == 0) return EKF_OK;
   *p = 0;
   return EKF_E_TIMEOUT;
@@ -642,7 +594,7 @@ int assoc_sync(ekf_ctx* h, int f0, int nf, bool predict, bool posterior, int m_m
     if (drain(h)) return EKF_E_HIP;
     for (int k = 0; k < nf; ++k) {
       FilterCtl c;
-      HIPCHK(hipMemcpy(&c, h->ctl + f0 + k, sizeof(FilterCtl), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&c, h->ctl.get() + f0 + k, sizeof(FilterCtl), hipMemcpyDeviceToHost));
       const int mf = h->plan.size(k);
       for (int i = i0; i < std::min(i1, mf); ++i) {
         if (j_out) j_out[static_cast<size_t>(k) * m_max + i] = c.assoc_j[i % kMaxAssoc];
@@ -661,10 +613,10 @@ int assoc_sync(ekf_ctx* h, int f0, int nf, bool predict, bool posterior, int m_m
 // *fl: the device word as read (nullable).
 int take_numeric(ekf_ctx* h, int f, unsigned* fl_out) {
   unsigned fl = 0;
-  HIPCHK(hipMemcpy(&fl, &h->ctl[f].status, sizeof(unsigned), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&fl, &h->ctl.get()[f].status, sizeof(unsigned), hipMemcpyDeviceToHost));
   if (fl & EKF_FLAG_NUMERIC) {
     const unsigned rest = fl & ~EKF_FLAG_NUMERIC;
-    HIPCHK(hipMemcpy(&h->ctl[f].status, &rest, sizeof(unsigned), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(&h->ctl.get()[f].status, &rest, sizeof(unsigned), hipMemcpyHostToDevice));
     h->held[f] |= EKF_FLAG_NUMERIC;
   }
   if (fl_out) *fl_out = fl;
@@ -696,7 +648,7 @@ int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* 
   // starts beside the planner instead of behind a main → bulk event hop (≈ 6 µs of each replay)
   const bool beside = h->devsync && !h->serial;
   // the bulk stream may still read the last descriptors (an idle one reads nothing: no hop)
-  if (hipStreamQuery(h->bulk) != hipSuccess && join_bulk(h)) return EKF_E_HIP;
+  if (hipStreamQuery(h->bulk.get()) != hipSuccess && join_bulk(h)) return EKF_E_HIP;
   // ... and the main stream: work there that the bulk stream is not ordered after (a k_posterior
   // of ekf_posterior reads its descriptor in ddesc) must end before a planner on the bulk stream
   // rewrites ddesc. (Chains are covered: the bulk stream's factor kernels follow every chain
@@ -705,7 +657,7 @@ int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* 
     if (fork_bulk(h)) return EKF_E_HIP;
     h->main_unordered = false;
   }
-  hipStream_t ps = beside ? h->bulk : h->stream;
+  hipStream_t ps = beside ? h->bulk.get() : h->stream.get();
   if (int rc = export_plan_state(h, ps)) return rc;
   ReplayArgs a{};
   a.counts = d_counts;
@@ -713,16 +665,16 @@ int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* 
   a.actions = d_actions;
   a.rel = d_rel_xy;
   a.odom = d_odom;
-  a.st_in = h->dstate[h->dstate_cur];
-  a.st_out = h->dstate[h->dstate_cur ^ 1];
-  a.desc = h->ddesc;
+  a.st_in = h->dstate[h->dstate_cur].get();
+  a.st_out = h->dstate[h->dstate_cur ^ 1].get();
+  a.desc = h->ddesc.get();
   a.T = T;
   a.joseph = h->plan.joseph() ? 1 : 0;
   a.F = h->F;
   a.M = m_max;
   a.N = h->cfg.n_landmarks;
-  a.stage = h->stage != nullptr;
-  a.plan_count = beside ? h->sync + kSyncPlan : nullptr;
+  a.stage = h->stage.get() != nullptr;
+  a.plan_count = beside ? h->sync.get() + kSyncPlan : nullptr;
   HIPCHK(launch_plan_replay(a, ps));
   h->dstate_cur ^= 1;
   h->plan_stream = ps;
@@ -735,7 +687,7 @@ int replay_device(ekf_ctx* h, int T, int m_max, const int* d_counts, const int* 
     if (fork_bulk(h)) return EKF_E_HIP;
   }
   h->main_dirty = false;
-  return issue_device_chunks(h, h->ddesc, T, false, h->stage != nullptr);
+  return issue_device_chunks(h, h->ddesc.get(), T, false, h->stage.get() != nullptr);
 }
 
 // Unknown-association replay whose inputs are already in device memory: k_plan_assoc writes the
@@ -759,7 +711,7 @@ int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const
   // that stream is ahead of it in stream order; work on the main stream that the bulk stream is
   // not ordered after yet (a chain, a k_posterior reading its descriptor) must end first: the hop a
   // host-planned association chunk takes (assoc_msg_group), taken before the planner instead.
-  hipStream_t ps = h->serial ? h->stream : h->bulk;
+  hipStream_t ps = h->serial ? h->stream.get() : h->bulk.get();
   if (!h->serial && (h->main_dirty || h->main_unordered) && fork_bulk_clean(h)) return EKF_E_HIP;
   if (ready) HIPCHK(hipStreamWaitEvent(ps, ready, 0));
   if (host_odom)
@@ -768,10 +720,10 @@ int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const
   AssocReplayArgs a{};
   a.counts = d_counts;
   a.xy = d_xy;
-  a.odom = host_odom ? h->odom_d : d_odom;
-  a.st_in = h->dstate[h->dstate_cur];
-  a.st_out = h->dstate[h->dstate_cur ^ 1];
-  a.desc = h->ddesc;
+  a.odom = host_odom ? h->odom_d.get() : d_odom;
+  a.st_in = h->dstate[h->dstate_cur].get();
+  a.st_out = h->dstate[h->dstate_cur ^ 1].get();
+  a.desc = h->ddesc.get();
   a.T = T;
   a.F = h->F;
   a.M = m_max;
@@ -786,7 +738,7 @@ int replay_device_assoc(ekf_ctx* h, int T, int m_max, const int* d_counts, const
   // launch of a host plan, this run's last publishes none (the next flush joins the bulk stream)
   int rc = EKF_OK;
   for (size_t i = 0; i < static_cast<size_t>(T) * C && !rc; ++i)
-    rc = assoc_msg_group(h, h->ddesc + i * F, 0, h->F, false);
+    rc = assoc_msg_group(h, h->ddesc.get() + i * F, 0, h->F, false);
   return rc;
 }
 
@@ -805,7 +757,7 @@ int replay_resident(ekf_ctx* h, int assoc, int T, int m_max, const int* d_counts
   const size_t no = 3 * static_cast<size_t>(T) * h->F;
   if (host_odom)
     if (int rc = stage_odom(h, host_odom, no)) return rc;
-  hipStream_t ps = h->stream;
+  hipStream_t ps = h->stream.get();
   if (ready) HIPCHK(hipStreamWaitEvent(ps, ready, 0));
   if (host_odom)
     if (int rc = upload_odom(h, no, ps)) return rc;
@@ -815,9 +767,9 @@ int replay_resident(ekf_ctx* h, int assoc, int T, int m_max, const int* d_counts
   r.ids = assoc ? nullptr : d_ids;
   r.actions = assoc ? nullptr : d_actions;
   r.xy = d_xy;
-  r.odom = host_odom ? h->odom_d : d_odom;
-  r.st_in = h->dstate[h->dstate_cur];
-  r.st_out = h->dstate[h->dstate_cur ^ 1];
+  r.odom = host_odom ? h->odom_d.get() : d_odom;
+  r.st_in = h->dstate[h->dstate_cur].get();
+  r.st_out = h->dstate[h->dstate_cur ^ 1].get();
   r.T = T;
   r.F = h->F;
   r.M = m_max;
@@ -868,8 +820,8 @@ int handle_info(ekf_t h, HandleInfo* out) {
   out->resident = h->resident;
   out->joseph = h->plan.joseph();
   out->serial = h->serial;
-  out->stream = h->stream;
-  out->bulk = h->bulk ? h->bulk : h->stream;
+  out->stream = h->stream.get();
+  out->bulk = h->bulk.get() ? h->bulk.get() : h->stream.get();
   return EKF_OK;
 }
 
@@ -890,7 +842,7 @@ int run_device_plan(ekf_t h, const MsgDesc* dd, const PlanEntry* dplan, int T,
     if (h->resident) {
       const PassArgs<double> a = args<double>(h, dd, 0);
       rc = timed(h, kProfResident, [&](hipEvent_t e0, hipEvent_t e1) {
-        return launch_resident(a, dplan, T, 0, h->F, h->stream, e0, e1);
+        return launch_resident(a, dplan, T, 0, h->F, h->stream.get(), e0, e1);
       });
     } else {
       // an owed Σ-pass epoch (the last flush's last pass published none): the chains take every

@@ -10,50 +10,43 @@
 
 #include "ekf.h"
 #include "ekf_internal.hpp"
+#include "hip_owned.hpp"
 #include "landmarks.h"
 #include "lm_launch.hpp"
 
 struct lm_ctx {
   int max_scans = 0, max_beams = 0, device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  float* d_ranges = nullptr;
-  double* d_amin = nullptr;
-  double* d_ainc = nullptr;
-  int* d_counts = nullptr;
-  lm_marker* d_markers = nullptr;
-  int marker_cap = 0;  // markers per scan the device buffer holds
-  lmk::DetectWork work{};
+  // (members are destroyed in reverse order: the stream outlives what is used on it)
+  ekfslam::Stream stream;
+  ekfslam::Event e0, e1;
+  ekfslam::DeviceBuf<float> d_ranges;
+  ekfslam::DeviceBuf<double> d_amin, d_ainc;
+  ekfslam::DeviceBuf<int> d_counts;
+  ekfslam::DeviceBuf<lm_marker> d_markers;  // [max_scans][markers per scan], grown on demand
+  lmk::DetectWork work{};                   // its pointers into these:
+  ekfslam::DeviceBuf<double> w_px, w_py;
+  ekfslam::DeviceBuf<lmk::Cand> w_cand;
+  ekfslam::DeviceBuf<int> w_gcount, w_sbase, w_sncand;
   // lm_fit_circles / lm_check_circles staging (grown on demand)
-  int* d_offs = nullptr;
-  double* d_xy = nullptr;
-  double* d_out = nullptr;
-  size_t cap_c = 0, cap_p = 0;
+  ekfslam::DeviceBuf<int> d_offs;
+  ekfslam::DeviceBuf<double> d_xy, d_out;
   bool timed = false;
   // lm_simulate: inputs on the device (the scenes grown on demand), the upload's event, the
   // kernel's timing events, and the scans resident in d_ranges
-  double* d_poses = nullptr;
-  int* d_scene = nullptr;
-  double* d_circles = nullptr;
-  size_t cap_circles = 0;  // doubles d_circles holds
-  hipEvent_t e_up = nullptr, s0 = nullptr, s1 = nullptr;
+  ekfslam::DeviceBuf<double> d_poses, d_circles;
+  ekfslam::DeviceBuf<int> d_scene;
+  ekfslam::Event e_up, s0, s1;
   bool sim_timed = false;
   int res_scans = 0, res_beams = 0;  // 0: nothing resident
   // lm_detect_device / lm_replay_into: the detect whose results stay in d_markers / d_counts
   // (dev_scans scans of dev_cap markers; 0: none), the event behind it that a filter's planning
   // stream waits for, and the event behind that planner which frees the marker buffer again
   int dev_scans = 0, dev_cap = 0;
-  hipEvent_t e_det = nullptr, e_planned = nullptr;
+  ekfslam::Event e_det{hipEventDisableTiming}, e_planned{hipEventDisableTiming};
   bool planner_reads = false;  // e_planned is recorded and this stream has not waited for it yet
 };
 
 namespace {
-
-int grow(void** p, size_t bytes) {
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  return hipMalloc(p, bytes) == hipSuccess ? EKF_OK : EKF_E_NOMEM;
-}
 
 // fitCircle / checkCircle inputs → device (offsets validated on the host)
 int stage_clusters(lm_t h, int nc, const int* offs, const double* xy) {
@@ -61,21 +54,14 @@ int stage_clusters(lm_t h, int nc, const int* offs, const double* xy) {
   for (int c = 0; c < nc; ++c)
     if (offs[c + 1] <= offs[c]) return EKF_E_ARG;
   const size_t np = static_cast<size_t>(offs[nc]);
-  if (static_cast<size_t>(nc) > h->cap_c) {
-    if (grow(reinterpret_cast<void**>(&h->d_offs), sizeof(int) * (nc + 1)) ||
-        grow(reinterpret_cast<void**>(&h->d_out), sizeof(double) * 3 * nc))
-      return EKF_E_NOMEM;
-    h->cap_c = nc;
-  }
-  if (np > h->cap_p) {
-    if (grow(reinterpret_cast<void**>(&h->d_xy), sizeof(double) * 2 * np)) return EKF_E_NOMEM;
-    h->cap_p = np;
-  }
+  const size_t c = static_cast<size_t>(nc);
+  if (h->d_offs.reserve(c + 1) || h->d_out.reserve(3 * c) || h->d_xy.reserve(2 * np))
+    return EKF_E_NOMEM;
   if (hipSetDevice(h->device) != hipSuccess ||
-      hipMemcpyAsync(h->d_offs, offs, sizeof(int) * (nc + 1), hipMemcpyHostToDevice, h->stream) !=
-          hipSuccess ||
-      hipMemcpyAsync(h->d_xy, xy, sizeof(double) * 2 * np, hipMemcpyHostToDevice, h->stream) !=
-          hipSuccess)
+      hipMemcpyAsync(h->d_offs.get(), offs, sizeof(int) * (nc + 1), hipMemcpyHostToDevice,
+                     h->stream.get()) != hipSuccess ||
+      hipMemcpyAsync(h->d_xy.get(), xy, sizeof(double) * 2 * np, hipMemcpyHostToDevice,
+                     h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
   return EKF_OK;
 }
@@ -85,22 +71,20 @@ int stage_clusters(lm_t h, int nc, const int* offs, const double* xy) {
 int enqueue_detect(lm_t h, int S, int B, double thr, int max_markers) {
   const int cap = max_markers > 0 ? max_markers : 1;
   h->dev_scans = 0;
+  const size_t need = static_cast<size_t>(h->max_scans) * cap;
   if (h->planner_reads) {  // a filter's planner (lm_replay_into) may still read markers and counts
-    if (cap > h->marker_cap && hipEventSynchronize(h->e_planned) != hipSuccess) return EKF_E_HIP;
-    if (hipStreamWaitEvent(h->stream, h->e_planned, 0) != hipSuccess) return EKF_E_HIP;
+    if (need > h->d_markers.capacity() && hipEventSynchronize(h->e_planned.get()) != hipSuccess)
+      return EKF_E_HIP;
+    if (hipStreamWaitEvent(h->stream.get(), h->e_planned.get(), 0) != hipSuccess) return EKF_E_HIP;
     h->planner_reads = false;
   }
-  if (cap > h->marker_cap) {
-    if (grow(reinterpret_cast<void**>(&h->d_markers),
-             sizeof(lm_marker) * static_cast<size_t>(h->max_scans) * cap))
-      return EKF_E_NOMEM;
-    h->marker_cap = cap;
-  }
-  if (hipEventRecord(h->e0, h->stream) != hipSuccess) return EKF_E_HIP;
-  if (lmk::launch_detect(h->d_ranges, S, B, h->d_amin, h->d_ainc, thr, h->d_markers, cap,
-                         h->d_counts, h->work, h->stream) != hipSuccess)
+  if (int rc = h->d_markers.reserve(need)) return rc;
+  if (hipEventRecord(h->e0.get(), h->stream.get()) != hipSuccess) return EKF_E_HIP;
+  if (lmk::launch_detect(h->d_ranges.get(), S, B, h->d_amin.get(), h->d_ainc.get(), thr,
+                         h->d_markers.get(), cap, h->d_counts.get(), h->work,
+                         h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
-  if (hipEventRecord(h->e1, h->stream) != hipSuccess) return EKF_E_HIP;
+  if (hipEventRecord(h->e1.get(), h->stream.get()) != hipSuccess) return EKF_E_HIP;
   h->timed = true;
   return EKF_OK;
 }
@@ -110,14 +94,14 @@ int run_detect(lm_t h, int S, int B, double thr, lm_marker* markers, int max_mar
                int* counts) {
   if (int rc = enqueue_detect(h, S, B, thr, max_markers)) return rc;
   const int cap = max_markers > 0 ? max_markers : 1;
-  if (hipMemcpyAsync(counts, h->d_counts, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream) !=
-      hipSuccess)
+  if (hipMemcpyAsync(counts, h->d_counts.get(), sizeof(int) * S, hipMemcpyDeviceToHost,
+                     h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
   if (max_markers > 0 &&
-      hipMemcpyAsync(markers, h->d_markers, sizeof(lm_marker) * static_cast<size_t>(S) * cap,
-                     hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+      hipMemcpyAsync(markers, h->d_markers.get(), sizeof(lm_marker) * static_cast<size_t>(S) * cap,
+                     hipMemcpyDeviceToHost, h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
-  return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  return hipStreamSynchronize(h->stream.get()) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 // A host caller's scans into the handle's buffers (enqueued).
@@ -125,11 +109,12 @@ int upload_scans(lm_t h, int S, int B, const float* ranges, const double* amin,
                  const double* ainc) {
   h->res_scans = h->res_beams = 0;  // the upload overwrites lm_simulate's scans
   const size_t nr = static_cast<size_t>(S) * B;
-  if (hipMemcpyAsync(h->d_ranges, ranges, sizeof(float) * nr, hipMemcpyHostToDevice, h->stream) !=
+  const hipStream_t st = h->stream.get();
+  if (hipMemcpyAsync(h->d_ranges.get(), ranges, sizeof(float) * nr, hipMemcpyHostToDevice, st) !=
           hipSuccess ||
-      hipMemcpyAsync(h->d_amin, amin, sizeof(double) * S, hipMemcpyHostToDevice, h->stream) !=
+      hipMemcpyAsync(h->d_amin.get(), amin, sizeof(double) * S, hipMemcpyHostToDevice, st) !=
           hipSuccess ||
-      hipMemcpyAsync(h->d_ainc, ainc, sizeof(double) * S, hipMemcpyHostToDevice, h->stream) !=
+      hipMemcpyAsync(h->d_ainc.get(), ainc, sizeof(double) * S, hipMemcpyHostToDevice, st) !=
           hipSuccess)
     return EKF_E_HIP;
   return EKF_OK;
@@ -147,32 +132,23 @@ int lm_create(lm_t* out, int max_scans, int max_beams, int device) {
   h->max_scans = max_scans;
   h->max_beams = max_beams;
   h->device = device;
-  const size_t S = max_scans;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess ||
-      hipEventCreate(&h->e0) != hipSuccess || hipEventCreate(&h->e1) != hipSuccess ||
-      hipEventCreate(&h->e_up) != hipSuccess || hipEventCreate(&h->s0) != hipSuccess ||
-      hipEventCreate(&h->s1) != hipSuccess ||
-      hipEventCreateWithFlags(&h->e_det, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->e_planned, hipEventDisableTiming) != hipSuccess) {
+  const size_t S = max_scans, SB = S * max_beams;
+  if (hipSetDevice(device) != hipSuccess || h->stream.create() || h->e0.create() ||
+      h->e1.create() || h->e_up.create() || h->s0.create() || h->s1.create() ||
+      h->e_det.create() || h->e_planned.create()) {
     lm_destroy(h);
     return EKF_E_HIP;
   }
-  if (hipMalloc(&h->d_ranges, sizeof(float) * S * max_beams) != hipSuccess ||
-      hipMalloc(&h->d_amin, sizeof(double) * S) != hipSuccess ||
-      hipMalloc(&h->d_ainc, sizeof(double) * S) != hipSuccess ||
-      hipMalloc(&h->d_counts, sizeof(int) * S) != hipSuccess ||
-      hipMalloc(&h->d_poses, sizeof(double) * 3 * S) != hipSuccess ||
-      hipMalloc(&h->d_scene, sizeof(int) * S) != hipSuccess ||
-      hipMalloc(&h->work.px, sizeof(double) * S * max_beams) != hipSuccess ||
-      hipMalloc(&h->work.py, sizeof(double) * S * max_beams) != hipSuccess ||
-      hipMalloc(&h->work.cand, sizeof(lmk::Cand) * lmk::candidate_capacity(max_scans, max_beams)) !=
-          hipSuccess ||
-      hipMalloc(&h->work.gcount, sizeof(int) * lmk::kRegions) != hipSuccess ||
-      hipMalloc(&h->work.sbase, sizeof(int) * S) != hipSuccess ||
-      hipMalloc(&h->work.sncand, sizeof(int) * S) != hipSuccess) {
+  if (h->d_ranges.reserve(SB) || h->d_amin.reserve(S) || h->d_ainc.reserve(S) ||
+      h->d_counts.reserve(S) || h->d_poses.reserve(3 * S) || h->d_scene.reserve(S) ||
+      h->w_px.reserve(SB) || h->w_py.reserve(SB) ||
+      h->w_cand.reserve(lmk::candidate_capacity(max_scans, max_beams)) ||
+      h->w_gcount.reserve(lmk::kRegions) || h->w_sbase.reserve(S) || h->w_sncand.reserve(S)) {
     lm_destroy(h);
     return EKF_E_NOMEM;
   }
+  h->work = lmk::DetectWork{h->w_px.get(),     h->w_py.get(),    h->w_cand.get(),
+                            h->w_gcount.get(), h->w_sbase.get(), h->w_sncand.get()};
   *out = h;
   return EKF_OK;
 }
@@ -180,21 +156,9 @@ int lm_create(lm_t* out, int max_scans, int max_beams, int device) {
 int lm_destroy(lm_t h) {
   if (!h) return EKF_E_ARG;
   hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  if (h->planner_reads) hipEventSynchronize(h->e_planned);  // a filter's planner reads d_markers
-  for (void* p : {static_cast<void*>(h->d_ranges), static_cast<void*>(h->d_amin),
-                  static_cast<void*>(h->d_ainc), static_cast<void*>(h->d_counts),
-                  static_cast<void*>(h->d_markers), static_cast<void*>(h->d_offs),
-                  static_cast<void*>(h->d_xy), static_cast<void*>(h->d_out),
-                  static_cast<void*>(h->work.px), static_cast<void*>(h->work.py),
-                  static_cast<void*>(h->work.cand), static_cast<void*>(h->work.gcount),
-                  static_cast<void*>(h->work.sbase), static_cast<void*>(h->work.sncand),
-                  static_cast<void*>(h->d_poses), static_cast<void*>(h->d_scene),
-                  static_cast<void*>(h->d_circles)})
-    if (p) hipFree(p);
-  for (hipEvent_t e : {h->e0, h->e1, h->e_up, h->s0, h->s1, h->e_det, h->e_planned})
-    if (e) hipEventDestroy(e);
-  if (h->stream) hipStreamDestroy(h->stream);
+  if (h->stream.get()) hipStreamSynchronize(h->stream.get());
+  // a filter's planner reads d_markers
+  if (h->planner_reads) hipEventSynchronize(h->e_planned.get());
   delete h;
   return EKF_OK;
 }
@@ -231,26 +195,22 @@ int lm_simulate(lm_t h, int S, int B, const double* poses, int G, int C, const d
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
   h->res_scans = h->res_beams = 0;
   const size_t nc = static_cast<size_t>(G) * C * 3;
-  if (nc > h->cap_circles) {
-    h->cap_circles = 0;
-    if (grow(reinterpret_cast<void**>(&h->d_circles), sizeof(double) * nc)) return EKF_E_NOMEM;
-    h->cap_circles = nc;
-  }
-  if (hipMemcpyAsync(h->d_poses, poses, sizeof(double) * 3 * S, hipMemcpyHostToDevice,
-                     h->stream) != hipSuccess ||
-      (nc && hipMemcpyAsync(h->d_circles, circles, sizeof(double) * nc, hipMemcpyHostToDevice,
-                            h->stream) != hipSuccess) ||
-      (scene && hipMemcpyAsync(h->d_scene, scene, sizeof(int) * S, hipMemcpyHostToDevice,
-                               h->stream) != hipSuccess) ||
-      hipEventRecord(h->e_up, h->stream) != hipSuccess)
+  if (int rc = h->d_circles.reserve(nc)) return rc;
+  if (hipMemcpyAsync(h->d_poses.get(), poses, sizeof(double) * 3 * S, hipMemcpyHostToDevice,
+                     h->stream.get()) != hipSuccess ||
+      (nc && hipMemcpyAsync(h->d_circles.get(), circles, sizeof(double) * nc, hipMemcpyHostToDevice,
+                            h->stream.get()) != hipSuccess) ||
+      (scene && hipMemcpyAsync(h->d_scene.get(), scene, sizeof(int) * S, hipMemcpyHostToDevice,
+                               h->stream.get()) != hipSuccess) ||
+      hipEventRecord(h->e_up.get(), h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
   lmk::ScanArgs a{};
-  a.poses = h->d_poses;
-  a.circles = h->d_circles;
-  a.scene = scene ? h->d_scene : nullptr;
-  a.ranges = h->d_ranges;
-  a.angle_min = h->d_amin;
-  a.angle_inc = h->d_ainc;
+  a.poses = h->d_poses.get();
+  a.circles = h->d_circles.get();
+  a.scene = scene ? h->d_scene.get() : nullptr;
+  a.ranges = h->d_ranges.get();
+  a.angle_min = h->d_amin.get();
+  a.angle_inc = h->d_ainc.get();
   a.n_scans = S;
   a.n_beams = B;
   a.n_circles = C;
@@ -261,17 +221,17 @@ int lm_simulate(lm_t h, int S, int B, const double* poses, int G, int C, const d
   a.range_min = cfg->range_min;
   a.range_max = cfg->range_max;
   a.sigma = cfg->sigma;
-  if (hipEventRecord(h->s0, h->stream) != hipSuccess ||
-      lmk::launch_scan(a, h->stream) != hipSuccess ||
-      hipEventRecord(h->s1, h->stream) != hipSuccess)
+  if (hipEventRecord(h->s0.get(), h->stream.get()) != hipSuccess ||
+      lmk::launch_scan(a, h->stream.get()) != hipSuccess ||
+      hipEventRecord(h->s1.get(), h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
   h->sim_timed = true;
   if (ranges_out) {
-    if (hipMemcpyAsync(ranges_out, h->d_ranges, sizeof(float) * static_cast<size_t>(S) * B,
-                       hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
+    if (hipMemcpyAsync(ranges_out, h->d_ranges.get(), sizeof(float) * static_cast<size_t>(S) * B,
+                       hipMemcpyDeviceToHost, h->stream.get()) != hipSuccess ||
+        hipStreamSynchronize(h->stream.get()) != hipSuccess)
       return EKF_E_HIP;
-  } else if (hipEventSynchronize(h->e_up) != hipSuccess) {  // the caller's inputs are consumed
+  } else if (hipEventSynchronize(h->e_up.get()) != hipSuccess) {  // the caller's inputs: consumed
     return EKF_E_HIP;
   }
   h->res_scans = S;
@@ -297,15 +257,15 @@ int lm_detect_device(lm_t h, int S, int B, const float* ranges, const double* am
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
   if (ranges) {
     if (int rc = upload_scans(h, S, B, ranges, amin, ainc)) return rc;
-    if (hipEventRecord(h->e_up, h->stream) != hipSuccess) return EKF_E_HIP;
+    if (hipEventRecord(h->e_up.get(), h->stream.get()) != hipSuccess) return EKF_E_HIP;
   } else {
     S = h->res_scans;
     B = h->res_beams;
   }
   if (int rc = enqueue_detect(h, S, B, thr, max_markers)) return rc;
-  if (hipEventRecord(h->e_det, h->stream) != hipSuccess) return EKF_E_HIP;
+  if (hipEventRecord(h->e_det.get(), h->stream.get()) != hipSuccess) return EKF_E_HIP;
   // the caller's scans are consumed (they may be freed); the detect itself is still in flight
-  if (ranges && hipEventSynchronize(h->e_up) != hipSuccess) return EKF_E_HIP;
+  if (ranges && hipEventSynchronize(h->e_up.get()) != hipSuccess) return EKF_E_HIP;
   h->dev_scans = S;
   h->dev_cap = max_markers;
   return EKF_OK;
@@ -317,14 +277,14 @@ int lm_fetch_markers(lm_t h, lm_marker* markers, int max_markers, int* counts) {
     return EKF_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
   const int S = h->dev_scans, w = max_markers < h->dev_cap ? max_markers : h->dev_cap;
-  if (counts && hipMemcpyAsync(counts, h->d_counts, sizeof(int) * S, hipMemcpyDeviceToHost,
-                               h->stream) != hipSuccess)
+  if (counts && hipMemcpyAsync(counts, h->d_counts.get(), sizeof(int) * S, hipMemcpyDeviceToHost,
+                               h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
-  if (w > 0 && hipMemcpy2DAsync(markers, sizeof(lm_marker) * max_markers, h->d_markers,
+  if (w > 0 && hipMemcpy2DAsync(markers, sizeof(lm_marker) * max_markers, h->d_markers.get(),
                                 sizeof(lm_marker) * h->dev_cap, sizeof(lm_marker) * w, S,
-                                hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+                                hipMemcpyDeviceToHost, h->stream.get()) != hipSuccess)
     return EKF_E_HIP;
-  return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  return hipStreamSynchronize(h->stream.get()) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 static_assert(sizeof(lm_marker) == 4 * sizeof(double), "k_plan_assoc reads lm_marker at stride 4");
@@ -336,9 +296,9 @@ int lm_replay_into(lm_t h, ekf_t e, int T, const double* odom) {
       static_cast<long long>(T) * F != h->dev_scans || h->dev_cap > 64)
     return EKF_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
-  const int rc = ekfslam::replay_markers(e, h->device, T, h->dev_cap, h->d_counts,
-                                         reinterpret_cast<const double*>(h->d_markers), odom,
-                                         h->e_det, h->e_planned);
+  const int rc = ekfslam::replay_markers(e, h->device, T, h->dev_cap, h->d_counts.get(),
+                                         reinterpret_cast<const double*>(h->d_markers.get()), odom,
+                                         h->e_det.get(), h->e_planned.get());
   // (an argument error comes back before anything is enqueued; past that the planner may be)
   if (rc != EKF_E_ARG) h->planner_reads = true;
   return rc;
@@ -352,9 +312,10 @@ int lm_replay_resident(lm_t h, ekf_t e, int T, const double* odom) {
     return EKF_E_ARG;
   if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
   // the filter's kernel reads the markers in place throughout: e_planned sits behind it
-  const int rc = ekfslam::replay_markers_resident(e, h->device, T, h->dev_cap, h->d_counts,
-                                                  reinterpret_cast<const double*>(h->d_markers),
-                                                  odom, h->e_det, h->e_planned);
+  const double* markers = reinterpret_cast<const double*>(h->d_markers.get());
+  const int rc = ekfslam::replay_markers_resident(e, h->device, T, h->dev_cap, h->d_counts.get(),
+                                                  markers, odom, h->e_det.get(),
+                                                  h->e_planned.get());
   if (rc != EKF_E_ARG) h->planner_reads = true;
   return rc;
 }
@@ -362,8 +323,9 @@ int lm_replay_resident(lm_t h, ekf_t e, int T, const double* odom) {
 int lm_last_simulate_us(lm_t h, double* us) {
   if (!h || !us || !h->sim_timed) return EKF_E_ARG;
   float ms = 0.0f;
-  if (hipEventSynchronize(h->s1) != hipSuccess ||  // lm_simulate may have left the kernel in flight
-      hipEventElapsedTime(&ms, h->s0, h->s1) != hipSuccess)
+  // (lm_simulate may have left the kernel in flight)
+  if (hipEventSynchronize(h->s1.get()) != hipSuccess ||
+      hipEventElapsedTime(&ms, h->s0.get(), h->s1.get()) != hipSuccess)
     return EKF_E_HIP;
   *us = 1e3 * ms;
   return EKF_OK;
@@ -372,29 +334,31 @@ int lm_last_simulate_us(lm_t h, double* us) {
 int lm_fit_circles(lm_t h, int nc, const int* offs, const double* xy, double* out) {
   if (!out) return EKF_E_ARG;
   if (int rc = stage_clusters(h, nc, offs, xy)) return rc;
-  if (lmk::launch_fit(nc, h->d_offs, h->d_xy, h->d_out, h->stream) != hipSuccess ||
-      hipMemcpyAsync(out, h->d_out, sizeof(double) * 3 * nc, hipMemcpyDeviceToHost, h->stream) !=
+  const hipStream_t st = h->stream.get();
+  if (lmk::launch_fit(nc, h->d_offs.get(), h->d_xy.get(), h->d_out.get(), st) != hipSuccess ||
+      hipMemcpyAsync(out, h->d_out.get(), sizeof(double) * 3 * nc, hipMemcpyDeviceToHost, st) !=
           hipSuccess)
     return EKF_E_HIP;
-  return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  return hipStreamSynchronize(h->stream.get()) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 int lm_check_circles(lm_t h, int nc, const int* offs, const double* xy, int* out) {
   if (!out) return EKF_E_ARG;
   for (int c = 0; offs && c < nc; ++c)
-    if (offs[c + 1] - offs[c] < 3) return EKF_E_ARG;  // the reference's angle vector needs n − 2 ≥ 1
+    if (offs[c + 1] - offs[c] < 3) return EKF_E_ARG;  // the reference's angle vector: n − 2 ≥ 1
   if (int rc = stage_clusters(h, nc, offs, xy)) return rc;
-  int* dout = reinterpret_cast<int*>(h->d_out);  // 3·nc doubles ≥ nc ints
-  if (lmk::launch_check(nc, h->d_offs, h->d_xy, dout, h->stream) != hipSuccess ||
-      hipMemcpyAsync(out, dout, sizeof(int) * nc, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+  int* dout = reinterpret_cast<int*>(h->d_out.get());  // 3·nc doubles ≥ nc ints
+  if (lmk::launch_check(nc, h->d_offs.get(), h->d_xy.get(), dout, h->stream.get()) != hipSuccess ||
+      hipMemcpyAsync(out, dout, sizeof(int) * nc, hipMemcpyDeviceToHost, h->stream.get()) !=
+          hipSuccess)
     return EKF_E_HIP;
-  return hipStreamSynchronize(h->stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  return hipStreamSynchronize(h->stream.get()) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 int lm_last_kernel_us(lm_t h, double* us) {
   if (!h || !us || !h->timed) return EKF_E_ARG;
   float ms = 0.0f;
-  if (hipEventElapsedTime(&ms, h->e0, h->e1) != hipSuccess) return EKF_E_HIP;
+  if (hipEventElapsedTime(&ms, h->e0.get(), h->e1.get()) != hipSuccess) return EKF_E_HIP;
   *us = 1e3 * ms;
   return EKF_OK;
 }

@@ -20,6 +20,7 @@
 #include "ekf_internal.hpp"
 #include "ekf_launch.hpp"
 #include "ekf_sim.h"
+#include "hip_owned.hpp"
 #include "sim_launch.hpp"
 
 using namespace ekfslam;
@@ -30,65 +31,50 @@ struct ekf_sim {
   HandleInfo info{};
   int L = 0, m = 0;
   long long tick = 0, msg = 0;  // global tick / message index of the next run
-  double* lm = nullptr;
-  unsigned* sighted = nullptr;
-  SimState* st = nullptr;
-  int* par = nullptr;
-  hipStream_t sst = nullptr;        // the simulator's stream
-  hipEvent_t ev_sim = nullptr;      // simulation of the current run done
-  hipEvent_t ev_done[2] = {nullptr, nullptr};  // filter work of the run that used buffer b done
-  int* host_par_pinned = nullptr;
-  SimState* host_st_pinned = nullptr;  // [F] poses after the last run (the handle's t_odom_robot)
+  // (members are destroyed in reverse order: the simulator's stream outlives what is used on it)
+  Stream sst;                             // the simulator's stream
+  DeviceBuf<double> lm;
+  DeviceBuf<unsigned> sighted;
+  DeviceBuf<SimState> st;
+  DeviceBuf<int> par;
+  Event ev_sim{hipEventDisableTiming};    // simulation of the current run done
+  // filter work of the run that used buffer b done
+  Event ev_done[2] = {Event{hipEventDisableTiming}, Event{hipEventDisableTiming}};
+  PinnedBuf<int> host_par_pinned;
+  PinnedBuf<SimState> host_st_pinned;  // [F] poses after the last run (the handle's t_odom_robot)
   int buf = 0;                      // run buffer of the next run
-  double* cmd[2] = {nullptr, nullptr};
-  int* sense[2] = {nullptr, nullptr};
-  size_t cap_ticks = 0, cap_msgs = 0;
-  MsgDesc* desc[2] = {nullptr, nullptr};
-  PlanEntry* plan = nullptr;
   // markers and poses of a run by run buffer: the record (cfg.record) and the parallel form's
   // hand-over to ekf_replay_device
   struct Markers {
-    int* ids = nullptr;       // [T][F][M]
-    int* act = nullptr;       // [T][F][M]
-    double* rel = nullptr;    // [T][F][M][2]
-    int* cnt = nullptr;       // [T][F]
-    double* truth = nullptr;  // [T][F][3]
-    double* odom = nullptr;   // [T][3] (filter 0's)
-    double* odomF = nullptr;  // [T][F][3] (the planner's input)
-  } mk[2];
-  bool mk_alloc = false;
-  int mk_bufs = 0;                  // marker buffers allocated (reserve)
-  bool assoc = false;               // ekf_sim_run_assoc has been called: both marker buffers, always
+    DeviceBuf<int> ids;       // [T][F][M]
+    DeviceBuf<int> act;       // [T][F][M]
+    DeviceBuf<double> rel;    // [T][F][M][2]
+    DeviceBuf<int> cnt;       // [T][F]
+    DeviceBuf<double> truth;  // [T][F][3]
+    DeviceBuf<double> odom;   // [T][3] (filter 0's)
+    DeviceBuf<double> odomF;  // [T][F][3] (the planner's input)
+  };
+  // What reserve() sizes for a run, all or nothing. `run = Run{}` frees member by member in this
+  // order, which is the order the buffers have always been freed in before a regrowth.
+  struct Run {
+    struct {
+      DeviceBuf<double> cmd;
+      DeviceBuf<int> sense;
+      DeviceBuf<MsgDesc> desc;
+    } in[2];  // by run buffer
+    DeviceBuf<PlanEntry> plan;
+    Markers mk[2];
+  } run;
+  // what `run` holds, recorded once all of it (the plan's upload included) is there
+  size_t cap_ticks = 0, cap_msgs = 0;
+  int mk_bufs = 0;                  // marker buffers allocated
+  bool assoc = false;  // ekf_sim_run_assoc has been called: both marker buffers, always
   int last_T = 0, last_b = 0;
   std::vector<int> host_par;
   std::vector<double> host_odom;    // [F][3] t_odom_robot after the last run
 };
 
 namespace {
-
-void free_run(ekf_sim* s) {
-  for (void* p : {static_cast<void*>(s->cmd[0]), static_cast<void*>(s->sense[0]),
-                  static_cast<void*>(s->desc[0]), static_cast<void*>(s->cmd[1]),
-                  static_cast<void*>(s->sense[1]), static_cast<void*>(s->desc[1]),
-                  static_cast<void*>(s->plan)})
-    if (p) hipFree(p);
-  for (auto& k : s->mk) {
-    for (void* p : {static_cast<void*>(k.ids), static_cast<void*>(k.act), static_cast<void*>(k.rel),
-                    static_cast<void*>(k.cnt), static_cast<void*>(k.truth),
-                    static_cast<void*>(k.odom), static_cast<void*>(k.odomF)})
-      if (p) hipFree(p);
-    k = ekf_sim::Markers{};
-  }
-  for (int b = 0; b < 2; ++b) {
-    s->cmd[b] = nullptr;
-    s->sense[b] = nullptr;
-    s->desc[b] = nullptr;
-  }
-  s->plan = nullptr;
-  s->mk_alloc = false;
-  s->mk_bufs = 0;
-  s->cap_ticks = s->cap_msgs = 0;
-}
 
 // The parallel form (no SURVEY message, HBM pipeline, M ≤ kMaxChunk; EKF_SIM_PARALLEL=0: never).
 bool parallel_ok(const ekf_sim* s, int T, const int* sense) {
@@ -113,37 +99,39 @@ int reserve(ekf_sim* s, int T) {
   // (the bulk stream too: an association replay of ekf_sim_run_assoc may still read the buffers)
   if (hipStreamSynchronize(s->info.stream) != hipSuccess ||
       hipStreamSynchronize(s->info.bulk) != hipSuccess ||
-      hipStreamSynchronize(s->sst) != hipSuccess)
+      hipStreamSynchronize(s->sst.get()) != hipSuccess)
     return EKF_E_HIP;
   const size_t Tn = std::max<size_t>({static_cast<size_t>(T), s->cap_msgs, 1});
-  free_run(s);
   const size_t tk = Tn * s->cfg.ticks_per_msg;
-  bool ok = hipMalloc(&s->plan, Tn * sizeof(PlanEntry)) == hipSuccess;
-  for (int b = 0; b < 2 && ok; ++b)
-    ok = hipMalloc(&s->cmd[b], tk * 2 * sizeof(double)) == hipSuccess &&
-         hipMalloc(&s->sense[b], Tn * sizeof(int)) == hipSuccess &&
-         hipMalloc(&s->desc[b], Tn * F * sizeof(MsgDesc)) == hipSuccess;
+  ekf_sim::Run& r = s->run;
+  // every buffer is freed before the first is allocated (bench.py's swarm workloads regrow inside
+  // their timed region: the order of the frees and allocations is part of what they measure)
+  r = ekf_sim::Run{};
+  s->cap_ticks = s->cap_msgs = 0;
+  s->mk_bufs = 0;
+  bool ok = !r.plan.reserve(Tn);
+  for (int b = 0; b < 2 && ok; ++b) {
+    auto& in = r.in[b];
+    ok = !(in.cmd.reserve(tk * 2) || in.sense.reserve(Tn) || in.desc.reserve(Tn * F));
+  }
   for (int b = 0; b < bufs && ok; ++b) {
-    auto& k = s->mk[b];
-    ok = hipMalloc(&k.ids, Tn * F * M * sizeof(int)) == hipSuccess &&
-         hipMalloc(&k.act, Tn * F * M * sizeof(int)) == hipSuccess &&
-         hipMalloc(&k.rel, Tn * F * M * 2 * sizeof(double)) == hipSuccess &&
-         hipMalloc(&k.cnt, Tn * F * sizeof(int)) == hipSuccess &&
-         hipMalloc(&k.truth, Tn * F * 3 * sizeof(double)) == hipSuccess &&
-         hipMalloc(&k.odom, Tn * 3 * sizeof(double)) == hipSuccess &&
-         hipMalloc(&k.odomF, Tn * F * 3 * sizeof(double)) == hipSuccess;
-    s->mk_alloc = ok;
+    auto& k = r.mk[b];
+    ok = !(k.ids.reserve(Tn * F * M) || k.act.reserve(Tn * F * M) ||
+           k.rel.reserve(Tn * F * M * 2) || k.cnt.reserve(Tn * F) || k.truth.reserve(Tn * F * 3) ||
+           k.odom.reserve(Tn * 3) || k.odomF.reserve(Tn * F * 3));
   }
-  if (!ok) {
-    free_run(s);
-    return EKF_E_NOMEM;
+  int rc = ok ? EKF_OK : EKF_E_NOMEM;
+  if (ok) {  // the resident plan: one entry per message, every filter (off = t·F)
+    std::vector<PlanEntry> pe(Tn);
+    for (size_t t = 0; t < Tn; ++t)
+      pe[t] = PlanEntry{static_cast<int>(t * F), 0, static_cast<int>(F), 0};
+    if (hipMemcpy(r.plan.get(), pe.data(), Tn * sizeof(PlanEntry), hipMemcpyHostToDevice) !=
+        hipSuccess)
+      rc = EKF_E_HIP;
   }
-  // the resident plan: one entry per message, every filter (off = t·F)
-  std::vector<PlanEntry> pe(Tn);
-  for (size_t t = 0; t < Tn; ++t) pe[t] = PlanEntry{static_cast<int>(t * F), 0, static_cast<int>(F), 0};
-  if (hipMemcpy(s->plan, pe.data(), Tn * sizeof(PlanEntry), hipMemcpyHostToDevice) != hipSuccess) {
-    free_run(s);  // no capacity is recorded for buffers whose plan never arrived
-    return EKF_E_HIP;
+  if (rc) {  // all or nothing: no capacity is recorded for buffers whose plan never arrived
+    r = ekf_sim::Run{};
+    return rc;
   }
   s->cap_msgs = Tn;
   s->cap_ticks = tk;
@@ -154,27 +142,27 @@ int reserve(ekf_sim* s, int T) {
 // The simulation of the parallel form into run buffer b, on the simulator's stream; the handle's
 // streams wait for it. Advances the tick and message counters.
 int simulate_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sense, int b) {
-  const hipStream_t st = s->sst;
+  const hipStream_t st = s->sst.get();
   const size_t ticks = static_cast<size_t>(T) * s->cfg.ticks_per_msg;
-  auto& k = s->mk[b];
+  auto& k = s->run.mk[b];
   // buffer b (commands, senses, markers) was last read by the run before the previous one
-  if (hipStreamWaitEvent(st, s->ev_done[b], 0) != hipSuccess ||
-      hipMemcpyAsync(s->cmd[b], wheel_cmd, ticks * 2 * sizeof(double), hipMemcpyHostToDevice, st) !=
-          hipSuccess ||
-      (sense && hipMemcpyAsync(s->sense[b], sense, T * sizeof(int), hipMemcpyHostToDevice, st) !=
-                    hipSuccess))
+  if (hipStreamWaitEvent(st, s->ev_done[b].get(), 0) != hipSuccess ||
+      hipMemcpyAsync(s->run.in[b].cmd.get(), wheel_cmd, ticks * 2 * sizeof(double),
+                     hipMemcpyHostToDevice, st) != hipSuccess ||
+      (sense && hipMemcpyAsync(s->run.in[b].sense.get(), sense, T * sizeof(int),
+                               hipMemcpyHostToDevice, st) != hipSuccess))
     return EKF_E_HIP;
   SimArgs a{};
-  a.cmd = s->cmd[b];
-  a.sense = sense ? s->sense[b] : nullptr;
-  a.lm = s->lm;
-  a.st = s->st;
-  a.out_ids = k.ids;
-  a.out_act = k.act;
-  a.out_rel = k.rel;
-  a.out_cnt = k.cnt;
-  a.out_truth = k.truth;
-  a.out_odom = s->cfg.record ? k.odom : nullptr;
+  a.cmd = s->run.in[b].cmd.get();
+  a.sense = sense ? s->run.in[b].sense.get() : nullptr;
+  a.lm = s->lm.get();
+  a.st = s->st.get();
+  a.out_ids = k.ids.get();
+  a.out_act = k.act.get();
+  a.out_rel = k.rel.get();
+  a.out_cnt = k.cnt.get();
+  a.out_truth = k.truth.get();
+  a.out_odom = s->cfg.record ? k.odom.get() : nullptr;
   a.seed = s->cfg.seed;
   a.tick0 = s->tick;
   a.msg0 = s->msg;
@@ -191,10 +179,10 @@ int simulate_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sen
   a.range = s->cfg.max_range;
   a.radius = s->cfg.wheel_radius;
   a.track = s->cfg.track_width;
-  if (launch_sim_parallel(a, k.truth, k.odomF, st) != hipSuccess ||
-      hipEventRecord(s->ev_sim, st) != hipSuccess ||
-      hipStreamWaitEvent(s->info.stream, s->ev_sim, 0) != hipSuccess ||
-      hipStreamWaitEvent(s->info.bulk, s->ev_sim, 0) != hipSuccess)
+  if (launch_sim_parallel(a, k.truth.get(), k.odomF.get(), st) != hipSuccess ||
+      hipEventRecord(s->ev_sim.get(), st) != hipSuccess ||
+      hipStreamWaitEvent(s->info.stream, s->ev_sim.get(), 0) != hipSuccess ||
+      hipStreamWaitEvent(s->info.bulk, s->ev_sim.get(), 0) != hipSuccess)
     return EKF_E_HIP;
   s->tick += static_cast<long long>(ticks);
   s->msg += T;
@@ -210,12 +198,12 @@ int run_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sense) {
   const int b = s->buf;
   s->buf ^= 1;
   if (int rc = simulate_parallel(s, T, wheel_cmd, sense, b)) return rc;
-  const auto& k = s->mk[b];
-  const int rc = ekf_replay_device(s->h, T, s->cfg.marker_stride, k.cnt, k.ids, k.act, k.rel,
-                                   k.odomF);
+  const auto& k = s->run.mk[b];
+  const int rc = ekf_replay_device(s->h, T, s->cfg.marker_stride, k.cnt.get(), k.ids.get(),
+                                   k.act.get(), k.rel.get(), k.odomF.get());
   if (rc) return rc;
   // the chain launch on the main stream polls the planner (or follows it): done there ⇒ read
-  return hipEventRecord(s->ev_done[b], s->info.stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  return hipEventRecord(s->ev_done[b].get(), s->info.stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 // ekf_sim_run_assoc: the same simulation, handed over with the ids ignored. Which stream reads the
@@ -228,14 +216,16 @@ int run_assoc(ekf_sim* s, int T, const double* wheel_cmd) {
   const int b = s->buf;
   s->buf ^= 1;
   if (int rc = simulate_parallel(s, T, wheel_cmd, nullptr, b)) return rc;
-  const auto& k = s->mk[b];
+  const auto& k = s->run.mk[b];
   const int M = s->cfg.marker_stride;
   const int rc = s->info.resident
-                     ? ekf_replay_resident(s->h, 1, T, M, k.cnt, nullptr, nullptr, k.rel, 2, k.odomF)
-                     : ekf_replay_device_assoc(s->h, T, M, k.cnt, k.rel, 2, k.odomF);
+                     ? ekf_replay_resident(s->h, 1, T, M, k.cnt.get(), nullptr, nullptr,
+                                           k.rel.get(), 2, k.odomF.get())
+                     : ekf_replay_device_assoc(s->h, T, M, k.cnt.get(), k.rel.get(), 2,
+                                               k.odomF.get());
   if (rc) return rc;
   const hipStream_t rs = s->info.resident || s->info.serial ? s->info.stream : s->info.bulk;
-  return hipEventRecord(s->ev_done[b], rs) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  return hipEventRecord(s->ev_done[b].get(), rs) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 }  // namespace
@@ -278,10 +268,13 @@ int ekf_sim_create(ekf_sim_t* out, ekf_t filter, const ekf_sim_config* cfg, int 
   }
   const size_t F = static_cast<size_t>(s->info.F), words = (n_map + 31) / 32;
   hipSetDevice(s->info.device);
-  bool ok = hipMalloc(&s->lm, F * n_map * 2 * sizeof(double)) == hipSuccess &&
-            hipMalloc(&s->sighted, F * words * sizeof(unsigned)) == hipSuccess &&
-            hipMalloc(&s->st, F * sizeof(SimState)) == hipSuccess &&
-            hipMalloc(&s->par, F * sizeof(int)) == hipSuccess;
+  auto fail = [&](int rc) {
+    ekf_sim_destroy(s);
+    return rc;
+  };
+  if (s->lm.reserve(F * n_map * 2) || s->sighted.reserve(F * words) || s->st.reserve(F) ||
+      s->par.reserve(F) || s->host_par_pinned.reserve(F) || s->host_st_pinned.reserve(F))
+    return fail(EKF_E_NOMEM);
   std::vector<SimState> st(F);
   for (auto& v : st) {
     std::memset(&v, 0, sizeof(v));
@@ -289,23 +282,15 @@ int ekf_sim_create(ekf_sim_t* out, ekf_t filter, const ekf_sim_config* cfg, int 
     v.truth[1] = cfg->start_x;
     v.truth[2] = cfg->start_y;
   }
-  ok = ok && hipStreamCreateWithFlags(&s->sst, hipStreamNonBlocking) == hipSuccess &&
-       hipEventCreateWithFlags(&s->ev_sim, hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&s->ev_done[0], hipEventDisableTiming) == hipSuccess &&
-       hipEventCreateWithFlags(&s->ev_done[1], hipEventDisableTiming) == hipSuccess &&
-       hipHostMalloc(reinterpret_cast<void**>(&s->host_par_pinned), F * sizeof(int),
-                     hipHostMallocDefault) == hipSuccess &&
-       hipHostMalloc(reinterpret_cast<void**>(&s->host_st_pinned), F * sizeof(SimState),
-                     hipHostMallocDefault) == hipSuccess &&
-       hipEventRecord(s->ev_done[0], s->info.stream) == hipSuccess &&
-       hipEventRecord(s->ev_done[1], s->info.stream) == hipSuccess &&
-       hipMemcpy(s->lm, landmarks, F * n_map * 2 * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemset(s->sighted, 0, F * words * sizeof(unsigned)) == hipSuccess &&
-       hipMemcpy(s->st, st.data(), F * sizeof(SimState), hipMemcpyHostToDevice) == hipSuccess;
-  if (!ok) {
-    ekf_sim_destroy(s);
-    return EKF_E_NOMEM;
-  }
+  if (s->sst.create(hipStreamNonBlocking) || s->ev_sim.create() || s->ev_done[0].create() ||
+      s->ev_done[1].create() ||
+      hipEventRecord(s->ev_done[0].get(), s->info.stream) != hipSuccess ||
+      hipEventRecord(s->ev_done[1].get(), s->info.stream) != hipSuccess ||
+      hipMemcpy(s->lm.get(), landmarks, F * n_map * 2 * sizeof(double), hipMemcpyHostToDevice) !=
+          hipSuccess ||
+      hipMemset(s->sighted.get(), 0, F * words * sizeof(unsigned)) != hipSuccess ||
+      hipMemcpy(s->st.get(), st.data(), F * sizeof(SimState), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(EKF_E_HIP);
   s->host_par.assign(F, 0);
   s->host_odom.assign(3 * F, 0.0);
   *out = s;
@@ -315,16 +300,7 @@ int ekf_sim_create(ekf_sim_t* out, ekf_t filter, const ekf_sim_config* cfg, int 
 int ekf_sim_destroy(ekf_sim_t s) {
   if (!s) return EKF_E_ARG;
   if (s->info.stream) hipStreamSynchronize(s->info.stream);
-  if (s->sst) hipStreamSynchronize(s->sst);
-  free_run(s);
-  for (void* p : {static_cast<void*>(s->lm), static_cast<void*>(s->sighted),
-                  static_cast<void*>(s->st), static_cast<void*>(s->par)})
-    if (p) hipFree(p);
-  if (s->host_par_pinned) hipHostFree(s->host_par_pinned);
-  if (s->host_st_pinned) hipHostFree(s->host_st_pinned);
-  for (hipEvent_t e : {s->ev_sim, s->ev_done[0], s->ev_done[1]})
-    if (e) hipEventDestroy(e);
-  if (s->sst) hipStreamDestroy(s->sst);
+  if (s->sst.get()) hipStreamSynchronize(s->sst.get());
   delete s;
   return EKF_OK;
 }
@@ -347,42 +323,41 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense) {
   if (par) return run_parallel(s, T, wheel_cmd, sense);
   const int b = s->buf;
   s->buf ^= 1;
-  const hipStream_t st = s->sst;
+  const hipStream_t st = s->sst.get();
   const size_t F = static_cast<size_t>(s->info.F);
   const size_t ticks = static_cast<size_t>(T) * s->cfg.ticks_per_msg;
   // the handle's host mirror is authoritative (host-planned calls between runs flip parities)
   if (int rc = handle_parity(s->h, s->host_par.data())) return rc;
-  std::memcpy(s->host_par_pinned, s->host_par.data(), F * sizeof(int));
-  if (hipMemcpyAsync(s->par, s->host_par_pinned, F * sizeof(int), hipMemcpyHostToDevice, st) !=
-      hipSuccess)
+  std::memcpy(s->host_par_pinned.get(), s->host_par.data(), F * sizeof(int));
+  if (hipMemcpyAsync(s->par.get(), s->host_par_pinned.get(), F * sizeof(int),
+                     hipMemcpyHostToDevice, st) != hipSuccess)
     return EKF_E_HIP;
   // buffer b was last read by the filter work of the run before the previous one
-  if (hipStreamWaitEvent(st, s->ev_done[b], 0) != hipSuccess) return EKF_E_HIP;
+  if (hipStreamWaitEvent(st, s->ev_done[b].get(), 0) != hipSuccess) return EKF_E_HIP;
   // (the record goes into marker buffer 0 whatever b is: a replay of the run before may read it)
-  if (s->cfg.record && b != 0 && hipStreamWaitEvent(st, s->ev_done[0], 0) != hipSuccess)
+  if (s->cfg.record && b != 0 && hipStreamWaitEvent(st, s->ev_done[0].get(), 0) != hipSuccess)
     return EKF_E_HIP;
-  if (hipMemcpyAsync(s->cmd[b], wheel_cmd, ticks * 2 * sizeof(double), hipMemcpyHostToDevice, st) !=
-      hipSuccess)
-    return EKF_E_HIP;
-  if (sense && hipMemcpyAsync(s->sense[b], sense, T * sizeof(int), hipMemcpyHostToDevice, st) !=
-                   hipSuccess)
+  if (hipMemcpyAsync(s->run.in[b].cmd.get(), wheel_cmd, ticks * 2 * sizeof(double),
+                     hipMemcpyHostToDevice, st) != hipSuccess ||
+      (sense && hipMemcpyAsync(s->run.in[b].sense.get(), sense, T * sizeof(int),
+                               hipMemcpyHostToDevice, st) != hipSuccess))
     return EKF_E_HIP;
   SimArgs a{};
-  a.cmd = s->cmd[b];
-  a.sense = sense ? s->sense[b] : nullptr;
-  a.lm = s->lm;
-  a.sighted = s->sighted;
-  a.st = s->st;
-  a.par = s->par;
-  a.desc = s->desc[b];
+  a.cmd = s->run.in[b].cmd.get();
+  a.sense = sense ? s->run.in[b].sense.get() : nullptr;
+  a.lm = s->lm.get();
+  a.sighted = s->sighted.get();
+  a.st = s->st.get();
+  a.par = s->par.get();
+  a.desc = s->run.in[b].desc.get();
   if (s->cfg.record) {
-    const auto& k = s->mk[0];
-    a.out_ids = k.ids;
-    a.out_act = k.act;
-    a.out_rel = k.rel;
-    a.out_cnt = k.cnt;
-    a.out_truth = k.truth;
-    a.out_odom = k.odom;
+    const auto& k = s->run.mk[0];
+    a.out_ids = k.ids.get();
+    a.out_act = k.act.get();
+    a.out_rel = k.rel.get();
+    a.out_cnt = k.cnt.get();
+    a.out_truth = k.truth.get();
+    a.out_odom = k.odom.get();
   }
   a.seed = s->cfg.seed;
   a.tick0 = s->tick;
@@ -403,26 +378,27 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense) {
   a.joseph = s->info.joseph && !s->info.resident;
   if (launch_sim(a, st) != hipSuccess) return EKF_E_HIP;
   // each filter's final parity (its inactive messages do not flip it) and odometry: the host mirror
-  if (hipMemcpyAsync(s->host_par_pinned, s->par, F * sizeof(int), hipMemcpyDeviceToHost, st) !=
-          hipSuccess ||
-      hipMemcpyAsync(s->host_st_pinned, s->st, F * sizeof(SimState), hipMemcpyDeviceToHost, st) !=
-          hipSuccess ||
-      hipEventRecord(s->ev_sim, st) != hipSuccess || hipEventSynchronize(s->ev_sim) != hipSuccess)
+  if (hipMemcpyAsync(s->host_par_pinned.get(), s->par.get(), F * sizeof(int),
+                     hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(s->host_st_pinned.get(), s->st.get(), F * sizeof(SimState),
+                     hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipEventRecord(s->ev_sim.get(), st) != hipSuccess ||
+      hipEventSynchronize(s->ev_sim.get()) != hipSuccess)
     return EKF_E_HIP;
-  std::memcpy(s->host_par.data(), s->host_par_pinned, F * sizeof(int));
+  std::memcpy(s->host_par.data(), s->host_par_pinned.get(), F * sizeof(int));
   for (size_t f = 0; f < F; ++f)
-    for (int k = 0; k < 3; ++k) s->host_odom[3 * f + k] = s->host_st_pinned[f].odom[k];
+    for (int k = 0; k < 3; ++k) s->host_odom[3 * f + k] = s->host_st_pinned.get()[f].odom[k];
   s->tick += static_cast<long long>(ticks);
   s->msg += T;
   s->last_T = T;
   s->last_b = 0;
   // the filter's kernels behind the simulation (their descriptors), then release buffer b
-  if (hipStreamWaitEvent(s->info.stream, s->ev_sim, 0) != hipSuccess) return EKF_E_HIP;
-  const int rc = run_device_plan(s->h, s->desc[b], s->plan, T, s->host_par.data(),
-                                 s->host_odom.data());
+  if (hipStreamWaitEvent(s->info.stream, s->ev_sim.get(), 0) != hipSuccess) return EKF_E_HIP;
+  const int rc = run_device_plan(s->h, s->run.in[b].desc.get(), s->run.plan.get(), T,
+                                 s->host_par.data(), s->host_odom.data());
   if (rc) return rc;
   if (int r2 = handle_info(s->h, &s->info)) return r2;  // joins the bulk stream into main
-  return hipEventRecord(s->ev_done[b], s->info.stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
+  return hipEventRecord(s->ev_done[b].get(), s->info.stream) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
 int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd) {
@@ -443,14 +419,16 @@ int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd) {
 int ekf_sim_markers(ekf_sim_t s, int* counts, int* ids, int* actions, double* rel_xy) {
   if (!s || !s->cfg.record) return EKF_E_ARG;
   const size_t n = static_cast<size_t>(s->last_T) * s->info.F, M = s->cfg.marker_stride;
-  const auto& k = s->mk[s->last_b];
+  const auto& k = s->run.mk[s->last_b];
   if (hipStreamSynchronize(s->info.stream) != hipSuccess ||
-      hipStreamSynchronize(s->sst) != hipSuccess)
+      hipStreamSynchronize(s->sst.get()) != hipSuccess)
     return EKF_E_HIP;
-  if ((counts && hipMemcpy(counts, k.cnt, n * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) ||
-      (ids && hipMemcpy(ids, k.ids, n * M * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) ||
-      (actions && hipMemcpy(actions, k.act, n * M * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) ||
-      (rel_xy && hipMemcpy(rel_xy, k.rel, n * M * 2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+  const auto d2h = [](void* dst, const void* src, size_t bytes) {  // (a null dst: not asked for)
+    return !dst || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+  };
+  if (!d2h(counts, k.cnt.get(), n * sizeof(int)) || !d2h(ids, k.ids.get(), n * M * sizeof(int)) ||
+      !d2h(actions, k.act.get(), n * M * sizeof(int)) ||
+      !d2h(rel_xy, k.rel.get(), n * M * 2 * sizeof(double)))
     return EKF_E_HIP;
   return EKF_OK;
 }
@@ -458,12 +436,14 @@ int ekf_sim_markers(ekf_sim_t s, int* counts, int* ids, int* actions, double* re
 int ekf_sim_poses(ekf_sim_t s, double* odom, double* truth) {
   if (!s || !s->cfg.record) return EKF_E_ARG;
   const size_t T = static_cast<size_t>(s->last_T);
-  const auto& k = s->mk[s->last_b];
+  const auto& k = s->run.mk[s->last_b];
   if (hipStreamSynchronize(s->info.stream) != hipSuccess ||
-      hipStreamSynchronize(s->sst) != hipSuccess)
+      hipStreamSynchronize(s->sst.get()) != hipSuccess)
     return EKF_E_HIP;
-  if ((odom && hipMemcpy(odom, k.odom, T * 3 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) ||
-      (truth && hipMemcpy(truth, k.truth, T * s->info.F * 3 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess))
+  if ((odom && hipMemcpy(odom, k.odom.get(), T * 3 * sizeof(double), hipMemcpyDeviceToHost) !=
+                   hipSuccess) ||
+      (truth && hipMemcpy(truth, k.truth.get(), T * s->info.F * 3 * sizeof(double),
+                          hipMemcpyDeviceToHost) != hipSuccess))
     return EKF_E_HIP;
   return EKF_OK;
 }
@@ -473,20 +453,20 @@ int ekf_sim_eval(ekf_sim_t s, ekf_eval_rec* out) {
   hipSetDevice(s->info.device);
   // SimState::truth is final once the simulator's stream is idle (the filter's own work is waited
   // for by the evaluation, like any state read)
-  if (hipStreamSynchronize(s->sst) != hipSuccess) return EKF_E_HIP;
+  if (hipStreamSynchronize(s->sst.get()) != hipSuccess) return EKF_E_HIP;
   const double frame[3] = {s->cfg.start_theta, s->cfg.start_x, s->cfg.start_y};
-  return eval_device(s->h, s->st->truth, sizeof(SimState) / sizeof(double), s->lm, s->L, frame,
-                     out);
+  return eval_device(s->h, s->st.get()->truth, sizeof(SimState) / sizeof(double), s->lm.get(),
+                     s->L, frame, out);
 }
 
 int ekf_sim_eval_match(ekf_sim_t s, double max_dist, ekf_eval_rec* out, ekf_match_rec* match_out,
                        int* match) {
   if (!s || !out || !(max_dist >= 0.0)) return EKF_E_ARG;
   hipSetDevice(s->info.device);
-  if (hipStreamSynchronize(s->sst) != hipSuccess) return EKF_E_HIP;  // (as ekf_sim_eval)
+  if (hipStreamSynchronize(s->sst.get()) != hipSuccess) return EKF_E_HIP;  // (as ekf_sim_eval)
   const double frame[3] = {s->cfg.start_theta, s->cfg.start_x, s->cfg.start_y};
-  return eval_match_device(s->h, s->st->truth, sizeof(SimState) / sizeof(double), s->lm, s->L,
-                           frame, max_dist, out, match_out, match);
+  return eval_match_device(s->h, s->st.get()->truth, sizeof(SimState) / sizeof(double),
+                           s->lm.get(), s->L, frame, max_dist, out, match_out, match);
 }
 
 }  // extern "C"
