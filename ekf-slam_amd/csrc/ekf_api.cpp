@@ -256,7 +256,7 @@ int ekf_create(ekf_t* out, const ekf_config* cfg_in) {
     return fail(EKF_E_NOMEM);
   // staged rebuild operands (EKF_STAGE=0: every kLook chain gathers its own, tests compare the two)
   // The same many-filter handles skip it by default (EKF_STAGE=1 keeps it): there every message's
-  // k_patch_stage runs on the serial critical path (≈ 18 µs for 512 filters), more than the chains'
+  // k_stage runs on the serial critical path (≈ 18 µs for 512 filters), more than the chains'
   // own gathers cost (two rounds of ≈ 2 µs).
   const char* stage_env = std::getenv("EKF_STAGE");
   const size_t stage_bytes =

@@ -25,7 +25,8 @@
 //     for the Σ pass — and applies the step to its block and state.
 // The Σ pass (k_sigma_pass, ekf_sigma_pass.hip) then applies Σ_out = Σ_in + Q̄ − Kcatᵀ·Mcat once.
 // fp32 Σ: a chunk that commits a new landmark also writes the final Σ[U, U] in fp64 (ChunkRec::Pend,
-// the first sighting's 1e7 − (1e7 − δ), slam.cpp:130) for k_patch_stage, after a last exchange.
+// the first sighting's 1e7 − (1e7 − δ), slam.cpp:130) for the Σ pass's fp32 tiles, after a last
+// exchange.
 //
 // In exact arithmetic this equals the reference's sequential dense algebra; the decisions are the
 // reference's (tests/test_gpu_scale.py: every decision equal to the oracle's, new and known
@@ -894,7 +895,7 @@ __device__ __forceinline__ void write_predict_factors(const AmFilter<T>& F, int 
                                                       const double* pose) {
   const T* S = F.S;
   const int ix = F.ix, ld = F.ld, lane = F.lane;
-  const int rank = 2 + (J ? 4 : 2) * m, kw = ((rank + 3) / 4) * 4;
+  const int rank = 2 + (J ? 4 : 2) * m, kw = pass_kw(J, m);
   if (F.valid) {
     // Σ_in[ix + e][0] and Σ_in[0][ix + e] (raw, as slot_block read them)
     const double c0[2] = {static_cast<double>(S[static_cast<size_t>(ix) * ld]),
@@ -944,9 +945,9 @@ __device__ __forceinline__ void finish_filter(const AmFilter<T>& F, const MsgDes
 }
 
 // fp32 Σ: the final Σ[U, U] in fp64 over the pass's block when a landmark was committed
-// (k_patch_stage; its first sighting cancels 1e7 − (1e7 − δ) in fp32); otherwise the record's flag
-// is cleared. G > 1: the final blocks (cur[m]) and every history row are published, then, after a
-// last exchange, workgroup 0 alone builds the block.
+// (the Σ pass's fp32 tiles take it; its first sighting cancels 1e7 − (1e7 − δ) in fp32); otherwise
+// the record's flag is cleared. G > 1: the final blocks (cur[m]) and every history row are
+// published, then, after a last exchange, workgroup 0 alone builds the block.
 template <typename T, bool J>
 __device__ __forceinline__ void write_pend_patch(AmSharedT<J>& sh, const AmFilter<T>& F,
                                                  ChunkRec* rec, int m, unsigned tag, unsigned spin,

@@ -32,7 +32,7 @@
 //   fold_predict              A3: this chunk's predict on the block
 //   chain_wave0 (_lean) .. 3  A2: the corrections; Z (wave 1), Y (wave 2), the rest of the block,
 //                             the posterior t_map_odom and the next predicted pose (wave 3)
-//   write_pend_patch          fp32: the final Σ[U, U] in fp64 for k_patch_stage
+//   write_pend_patch          fp32: the final Σ[U, U] in fp64 for the Σ pass's tiles
 //   write_record              ChunkRec, write-through
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -517,7 +517,7 @@ __device__ __noinline__ int chain_wave0_lean(LdsChain<J>* shp, LdsDesc* dp, int 
 // The previous chunk's predict on the rebuild operands: v + α_i·Σ[0][j] +
 // (Σ[i][0] + α_i·Σ00)·α_j + Q̄, for D = Σ_in'[U, U] → im.D, R = Σ_in'[U, U'] → im.R and
 // C = Σ_in'[U', U] → im.C (R / C columns k ≥ |U'| up to 36 zero: MFMA k padding). The raw blocks
-// are in LDS first — a staged image (k_patch_stage) copied in, or a gathering chain's own loads
+// are in LDS first — a staged image (k_stage) copied in, or a gathering chain's own loads
 // (thread tid's entries e = tid + i·256 of the 36 × 36 block) — then predict_prev applies the
 // predict from the raw row 0 / column 0 (pv.r0U, c0U, r0P, c0P; pv.first, a1, a2).
 constexpr int kChainThreads = 256;
@@ -544,7 +544,7 @@ __device__ __forceinline__ void special_entry(int s, int& a, int& b) {
 }
 
 // A gathering chain's raw blocks, stored at the image's positions with the image's zeros (what
-// k_patch_stage stores for a staged chain): thread tid's entries e = tid + 256·i = (a, b) of the
+// k_stage stores for a staged chain): thread tid's entries e = tid + 256·i = (a, b) of the
 // 36-wide blocks, C transposed.
 template <typename T, typename Shared>
 __device__ __forceinline__ void store_raw_image(Shared& sh, const T (&vd)[kRebPer],
@@ -655,7 +655,7 @@ __device__ __forceinline__ void load_prev_record(ChainLoads<T, J>& L, __amdgpu_b
 
 // kLook with staged operands: the loads do not depend on A0's index sets, so they are issued
 // before it and land during A0 (whose barrier orders LDS only). The image was staged by the
-// k_patch_stage two chunks back, right behind the Σ pass that wrote Σ_in': the same values as the
+// k_stage two chunks back, right behind the Σ pass that wrote Σ_in': the same values as the
 // gather of land_rebuild_operands, in the LDS image's layout (≈ 5 000 cycles less than the ≈ 1 900
 // scattered lines of the gather through one CU). Issued unconditionally, through buffer descriptors
 // of size 0 unless `early` (zeros, no access): a load under a branch is waited for at the branch's
@@ -1649,7 +1649,7 @@ __device__ __forceinline__ void chain_wave2(ChainSharedT<J>& sh, ChunkRec* rec, 
 
 // ---- the fp32 pend patch -------------------------------------------------------------------------
 // fp32 Σ: the last step's rank-2 term on the whole block (earlier steps are applied), the final
-// Σ[U, U] in fp64, to the record (write-through) for k_patch_stage (the Σ pass's U × U entries).
+// Σ[U, U] in fp64, to the record (write-through) for the Σ pass's fp32 tiles (their U × U entries).
 // Only a chunk that initialises a landmark has the 1e7 − (1e7 − δ) cancellation the patch is
 // for (slam.cpp:130's prior has no cross terms; an untouched landmark's rows stay exact): a first
 // sighting, or an association chunk (its new landmark is written by k_assoc). Other chunks keep

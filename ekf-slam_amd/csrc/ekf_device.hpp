@@ -22,8 +22,10 @@ constexpr int kMaxJoseph = kMaxChunk;            // markers of a Joseph-form chu
                                                  // message, one Σ pass); its row map Z holds K's and
                                                  // V's columns, 4 per marker
 constexpr int kZJ = 4 * kMaxJoseph;              // the record's Z columns (Joseph: Z then Zv)
-// rank of the fused update, padded to 4: 2 + 2m (simple form), 2 + 4m (Joseph form)
-constexpr int kMaxKW = ((2 + 4 * kMaxJoseph + 3) / 4) * 4;
+// rank of a chunk's fused update, padded to 4: 2 + 2m (simple form), 2 + 4m (Joseph form: K·M and
+// V·Kᵀ per marker). Kcat / Mcat rows beyond it are stale. (constexpr: host and device)
+constexpr int pass_kw(bool joseph, int m) { return ((2 + (joseph ? 4 : 2) * m + 3) / 4) * 4; }
+constexpr int kMaxKW = pass_kw(true, kMaxJoseph);
 
 // Device epochs (unsigned words of the handle's sync buffer, each polled word on its own line):
 constexpr int kSyncSigma = 0;    // epoch (seq + 1) of the last complete Σ pass (k_sigma_epoch)
@@ -41,7 +43,7 @@ constexpr int kLook = 16;    // Σ_in not materialised yet: rebuild the chain's 
                              // previous chunk's Σ_in (other buffer) and ChunkRec
 constexpr int kJoseph = 128; // Joseph-form Σ update (ekf_set_joseph): ≤ kMaxJoseph markers per
                              // chunk, the factor rank 2 + 4m (K·M and (ΣHᵀ − K·S)·Kᵀ, see k_chain)
-constexpr int kStageOut = 256;  // behind this chunk's Σ pass (k_patch_stage): gather the rebuild
+constexpr int kStageOut = 256;  // behind this chunk's Σ pass (k_stage): gather the rebuild
                                 // operands of the filter's chunk after next (stg_*) into StageRec
 constexpr int kStageIn = 512;   // kLook chain: read its rebuild operands from StageRec (contiguous)
                                 // instead of gathering them from Σ_in' at the chunk's start
@@ -114,7 +116,7 @@ static_assert(offsetof(ChunkRec, Z) % 16 == 0 && offsetof(ChunkRec, Y) % 16 == 0
               "ChunkRec payload 16-byte aligned");
 
 // The rebuild operands of a kLook chain (k_chain's prologue), gathered off the chain's path by the
-// k_patch_stage of the chunk two back, right behind the Σ pass that wrote them: with U this chunk's
+// k_stage of the chunk two back, right behind the Σ pass that wrote them: with U this chunk's
 // index set and U' the previous chunk's, Σ = Σ_in' (the previous chunk's Σ_in), x = x_in',
 //   im.D[a][b] = Σ[u_a][u_b], im.R[a][k] = Σ[u_a][u'_k], im.C[k][a] = Σ[u'_k][u_a]
 //   r0u[t] = Σ[0][u_t], c0u[t] = Σ[u_t][0], r0p[t] = Σ[0][u'_t], c0p[t] = Σ[u'_t][0], xg[t] = x[u_t]

@@ -98,10 +98,10 @@ template <typename T>
 hipError_t launch_factors(const PassArgs<T>& a, int n_filters, hipStream_t s,
                       hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
-// Σ pass: Σ_out = Σ_in + Q − Kcatᵀ·Mcat on MFMA, one tile per wave, then k_patch_stage (fp32: the
-// chain's fp64 Σ[U,U] over its block; stage: some filter's descriptor has kStageOut, fp32 checks
-// on the device). publish: launch the Σ-pass epoch kernel behind it; otherwise the next chunk's
-// factor kernel publishes it (PassArgs::pub_sigma).
+// Σ pass: Σ_out = Σ_in + Q − Kcatᵀ·Mcat on MFMA, one tile per wave (fp32: the tiles also write the
+// chain's fp64 Σ[U,U] over its block, ChunkRec::Pend), on the grid of sigma_grid.hpp. stage: some
+// filter's descriptor has kStageOut, so k_stage follows. publish: launch the Σ-pass epoch kernel
+// behind it; otherwise the next chunk's factor kernel publishes it (PassArgs::pub_sigma).
 template <typename T>
 hipError_t launch_sigma_pass(const PassArgs<T>& a, int n_filters, bool publish, bool stage, hipStream_t s,
                       hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

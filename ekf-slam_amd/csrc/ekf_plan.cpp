@@ -132,7 +132,7 @@ void Planner::known(int f0, int nf, bool predict, const char* absent) {
         d->z[i][0] = mk[b + i].zr;
         d->z[i][1] = mk[b + i].zb;
       }
-      // the k_patch_stage behind the Σ pass two chunks back gathers this chain's rebuild operands
+      // the k_stage behind the Σ pass two chunks back gathers this chain's rebuild operands
       // (the Σ_in' it reads is that pass's output)
       const Staged two_back = staged_[f][1];
       if ((flags & kLook) && staging_ && two_back.desc >= 0) {
@@ -151,7 +151,7 @@ void Planner::known(int f0, int nf, bool predict, const char* absent) {
       prev_m_[f] = m;
       for (int i = 0; i < m; ++i) prev_ids_[f][i] = mk[b + i].id;
       parity_[f] ^= 1;
-      kw = std::max(kw, ((2 + (jos ? 4 : 2) * m + 3) / 4) * 4);
+      kw = std::max(kw, pass_kw(jos, m));
       if (chunk == 0) pending_[f] = 0;
     }
     plan_l_[li].kw = kw;

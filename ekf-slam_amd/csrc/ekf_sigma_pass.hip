@@ -1,6 +1,7 @@
 // k_sigma_pass (gfx950 / CDNA4): the third kernel of a chunk (ekf_chain.hip's header has the
 // three), the rank-(2+2m) update of the dense covariance from the factor kernel's Kcat / Mcat, with
-// what runs right behind it on its stream: k_patch_stage and the Σ-pass epoch.
+// what runs right behind it on its stream: k_stage and the Σ-pass epoch. The pass's tile grid, for
+// the launcher and the kernel alike, is sigma_grid.hpp's.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include "ekf_device.hpp"
 #include "ekf_launch.hpp"
 #include "ekf_math.hpp"
+#include "sigma_grid.hpp"
 
 namespace ekfslam {
 
@@ -64,15 +66,6 @@ struct SigmaTile<float> {
     const int col = C0 + (lane & 31);
     return col < n ? static_cast<unsigned>(4 * (lane >> 5) * ld + col) * 4u : kOOB;
   }
-  // every load of the tile: the operands (L2-hot) first, then Σ_in
-  static __device__ __forceinline__ void load(F32TileRegs& g, const float* Sin, const float* kc,
-                                              const float* mc, int n, int ld, int ldk, int R0,
-                                              int C0, int lane) {
-    load_ops(g, kc, mc, n, ldk, R0, C0, lane);
-    // keep the operand loads ahead of Σ_in's: the MFMAs then wait for vmcnt(16), not vmcnt(0)
-    __builtin_amdgcn_sched_barrier(0);
-    load_sig(g, Sin, n, ld, R0, C0, lane);
-  }
   // block kb: factor rows 2·kSteps·kb + 2s + (lane ≥ 32)
   static __device__ __forceinline__ void load_ops(F32TileRegs& g, const float* kc, const float* mc,
                                                   int n, int ldk, int R0, int C0, int lane,
@@ -98,18 +91,9 @@ struct SigmaTile<float> {
 #pragma unroll
     for (int r = 0; r < 16; ++r) g.sv[r] = ld_f32(rin, so + ((r & 3) + 8 * (r >> 2)) * rstride, 0);
   }
-  static __device__ __forceinline__ void run(const float* Sin, float* Sout, const float* kc,
-                                             const float* mc, int n, int ld, int ldk, int kw,
-                                             bool first, double qd, int R0, int C0, int lane,
-                                             float*) {
-    F32TileRegs g;
-    load(g, Sin, kc, mc, n, ld, ldk, R0, C0, lane);
-    finish(g, Sout, n, ld, kw, first, qd, R0, C0, lane);
-  }
   // the MFMAs on the tile's operands, Σ_in − K·M (+ Q̄), the stores
-  // pm (≠ null: the chunk's record holds the chain's fp64 Σ[U, U], kPendValid): the first position
-  // in U of each tile row (pm[0..32)) and column (pm[32..64)), > kMaxU − 1 for none — those
-  // entries take the record's value instead (what k_patch_stage wrote after the pass before)
+  // pm (≠ null: the chunk's record holds the chain's fp64 Σ[U, U], kPendValid): the tile's patch
+  // map (patch_map below) — the entries whose row and column are both in U take the record's value
   static __device__ __forceinline__ void finish(const F32TileRegs& g, float* Sout, int n, int ld,
                                                 int kw, bool first, double qd, int R0, int C0,
                                                 int lane, const int* pm = nullptr,
@@ -303,256 +287,155 @@ struct SigmaTile64 {
     }
   }
 };
-// the tiles of a symmetric pass: tile row tr holds tile columns ⌊32·tr / kCols⌋ … tcols − 1
-template <int kCols>
-__host__ __device__ inline int sym_first(int tr) { return 32 * tr / kCols; }
-template <int kCols>
-__host__ __device__ inline int sym_tiles(int trows, int tcols) {
-  int t = 0;
-  for (int tr = 0; tr < trows; ++tr) t += tcols - sym_first<kCols>(tr);
-  return t;
-}
-// the t-th of them, row-major (wave-uniform t: a scalar walk over the tile rows)
-template <int kCols>
-__device__ __forceinline__ bool sym_tile(int t, int trows, int tcols, int& tr, int& tc) {
-  int base = 0;
-  for (tr = 0; tr < trows; ++tr) {
-    const int c = tcols - sym_first<kCols>(tr);
-    if (t < base + c) break;
-    base += c;
-  }
-  tc = tr < trows ? sym_first<kCols>(tr) + (t - base) : 0;
-  return tr < trows;
-}
 template <>
 struct SigmaTile<double> : SigmaTile64<2> {};
 // the tile a Σ pass of T runs: WIDE (swarms) takes the 32 × 64 fp64 tile
 template <typename T, bool WIDE>
 using PassTile = typename std::conditional<sizeof(T) == 8 && WIDE, SigmaTile64<4>, SigmaTile<T>>::type;
+constexpr int kPassWaves = 4;  // waves (= tiles) per workgroup
 
-// xcd_b = 0: grid (blocks per filter, filters). xcd_b = B > 0 (many filters): a 1-D grid whose
-// block L runs on XCD L % 8 (dispatch deals blocks round-robin over the XCDs); it is given filter
-// 8·⌊(L/8)/B⌋ + L % 8, tile block (L/8) % B, so all of a filter's blocks share one XCD and its
-// Kcat/Mcat are fetched into one L2 instead of eight. Placement only changes speed.
-// Waves take tiles row-major over a trows × tcols grid.
-// xcd_b = −1 (few filters, one per blockIdx.y): the tile grid is cut 2 × 4 into regions, block L
-// takes region L % 8 (so XCD L % 8 does): each XCD's L2 then fetches half of Kcat and a quarter
-// of Mcat instead of both whole (the fetch beyond Σ: 8 × (Kcat + Mcat) → 4 × Kcat + 2 × Mcat).
-constexpr int kRegRows = 2, kRegCols = 4;
-__host__ __device__ inline int region_tiles(int trows, int tcols) {  // the largest region's tiles
-  return ((trows + kRegRows - 1) / kRegRows) * ((tcols + kRegCols - 1) / kRegCols);
+// The fp32 tile's patch map, in the wave's 64 ints of LDS: pm[0..32) the first position in the
+// chunk's U (rec->u[0..nu)) of each of the tile's rows R0 … R0 + 31, pm[32..64) of each of its
+// columns C0 … C0 + 31; kMaxU (> any position) for a row / column not in U. Each lane brings one
+// position of U; an index listed twice keeps its first position (atomicMin). Within the wave only:
+// the fences order its LDS accesses, no barrier.
+__device__ __forceinline__ const int* patch_map(int* map, const ChunkRec* rec, int R0, int C0,
+                                                int lane) {
+  map[lane] = kMaxU;
+  const int nu = rec->nu, u = rec->u[min(lane, kMaxU - 1)];
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  if (lane < nu && u >= R0 && u < R0 + 32) atomicMin(&map[u - R0], lane);
+  if (lane < nu && u >= C0 && u < C0 + 32) atomicMin(&map[32 + u - C0], lane);
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  return map;
 }
+
+// One fp32 tile (tr, tc) of filter A.f0 + fb. The operand loads depend only on the filter and the
+// tile, so they go out before the descriptor's scalar round trips (flags, parity, m, then the Σ
+// pointer it selects) instead of behind them (≈ 0.3 µs of a 9 µs pass, tools/pass_lab.hip).
+// map: the wave's 64 ints of LDS (patch_map).
+template <int KB>
+__device__ __forceinline__ void pass_tile_f32(const PassArgs<float>& A, const MsgDesc& d, int fb,
+                                              int tr, int tc, int lane, int* map) {
+  using Tile = SigmaTile<float>;
+  const int f = A.f0 + fb;
+  const int R0 = tr * Tile::kRows, C0 = tc * Tile::kCols;
+  // the patch test's record flags of both parities, issued with the operands (not a scalar round
+  // trip behind the descriptor's parity: that wait cost ≈ 0.4 µs of the pass)
+  const int rf0 = A.rec[f].flags, rf1 = A.rec[A.rec_stride + f].flags;
+  F32TileRegs g;
+  Tile::load_ops(g, A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.n, A.ldk, R0, C0, lane);
+  // keep the operand loads ahead of Σ_in's: the MFMAs then wait for vmcnt(16), not vmcnt(0)
+  __builtin_amdgcn_sched_barrier(0);
+  if (!(d.flags & kActive)) return;
+  SIG_STAMP(1);
+  const int kw = pass_kw((d.flags & kJoseph) != 0, d.m);
+  Tile::load_sig(g, A.sig[d.parity] + f * A.sig_stride, A.n, A.ld, R0, C0, lane);
+  // the fp32 patch: the chain's fp64 Σ[U, U] over this tile's entries there, for the chunks that
+  // initialised a landmark (the pass's 1e7 − (1e7 − δ) at a first sighting — the reference's
+  // prior, slam.cpp:130 — loses δ in fp32)
+  const ChunkRec* rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
+  const int* pm = nullptr;
+  if ((d.parity ? rf1 : rf0) & kPendValid) pm = patch_map(map, rec, R0, C0, lane);  // wave-uniform
+  float* Sout = A.sig[d.parity ^ 1] + f * A.sig_stride;
+  const bool first = (d.flags & kFirst) != 0;
+  if constexpr (KB == 1)
+    Tile::finish(g, Sout, A.n, A.ld, kw, first, A.q, R0, C0, lane, pm, rec);
+  else
+    Tile::finish2(g, A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.ldk, Sout, A.n, A.ld, kw,
+                  first, A.q, R0, C0, lane, pm, rec);
+}
+
+// One fp64 tile (SigmaTile64) of filter A.f0 + fb. tT: the wave's Tile::kLds doubles of LDS.
+template <typename Tile, int KB>
+__device__ __forceinline__ void pass_tile_f64(const PassArgs<double>& A, const MsgDesc& d, int fb,
+                                              int tr, int tc, int lane, double* tT) {
+  if (!(d.flags & kActive)) return;
+  SIG_STAMP(1);
+  const int f = A.f0 + fb;
+  // this filter's rank; rows beyond are stale
+  const int kw = pass_kw((d.flags & kJoseph) != 0, d.m);
+  Tile::template run<KB>(A.sig[d.parity] + f * A.sig_stride, A.sig[d.parity ^ 1] + f * A.sig_stride,
+                         A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.n, A.ld, A.ldk, kw,
+                         (d.flags & kFirst) != 0, A.q, tr * Tile::kRows, tc * Tile::kCols, lane, tT);
+}
+
 // An explicit occupancy target (the one the registers allowed anyway: 2 waves/SIMD for the wide
 // fp64 tile, 4–5 for the narrow one, 6–7 for fp32) makes the allocator keep the MFMA accumulators
 // in VGPRs instead of AGPRs (no v_accvgpr_read before the Σ_in subtraction and the stores): swarm
 // message 0.719 → 0.703 ms, N = 1024 fp64 pass 16.4 → 15.9 µs, fp32 unchanged
 // (profiles/r3/p3r_vgpr_acc_ab.txt, two alternating runs each)
-// KB: operand blocks of the rank (the Joseph form's instantiation: 2)
+// As it stands: PassTile<float, true> is the very tile PassTile<float, false> is, yet the fp32
+// swarm's instantiation k_sigma_pass<float, true, KB> is a kernel of its own with the target 2
+// where the narrow fp32 one has 6. Whether that is intended is a performance question; the
+// launcher's choice of instantiation (WIDE = many filters) is left as it is.
+template <typename T, bool WIDE>
+constexpr int kPassWavesPerEu = WIDE ? 2 : (sizeof(T) == 8 ? 4 : 6);
+// KB: operand blocks of the rank (the Joseph form's instantiation: 2). G: sigma_grid() of this
+// launch, the one the launcher sized its grid from.
 template <typename T, bool WIDE, int KB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WIDE ? 2 : (sizeof(T) == 8 ? 4 : 6)))) void k_sigma_pass(PassArgs<T> A, int tcols, int xcd_b, int nf) {
+__global__ __launch_bounds__(64 * kPassWaves)
+__attribute__((amdgpu_waves_per_eu(kPassWavesPerEu<T, WIDE>))) void k_sigma_pass(PassArgs<T> A,
+                                                                                 SigmaGrid G) {
   using Tile = PassTile<T, WIDE>;
-  SIG_STAMP(0);
-  int fb = blockIdx.y, bx = blockIdx.x;
-  if (xcd_b > 0) {
-    const int L = blockIdx.x, j = L >> 3;
-    fb = (L & 7) + 8 * (j / xcd_b);
-    bx = j % xcd_b;
-    if (fb >= nf) return;
-  }
-  const MsgDesc& d = A.desc[fb];
   constexpr bool kSym = sizeof(T) == 8;  // fp64: the symmetric tiles (SigmaTile64)
-  __shared__ int cmap[4][64];  // per wave (fp32 patch): tile row / column → first position in U
-  __shared__ double tT[kSym ? 4 : 1][kSym ? 16 * (WIDE ? 4 : 2) * kTS : 1];  // (SigmaTile64::kLds)
-  const int lane = threadIdx.x & 63;
-  const int trows = (A.n + Tile::kRows - 1) / Tile::kRows;
-  // the wave's tile index, provably wave-uniform (readfirstlane): the buffer descriptors built
-  // from it stay in SGPRs instead of a waterfall loop around every buffer access
-  int t = __builtin_amdgcn_readfirstlane(bx * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  int tr = 0, tc = 0;
-  bool ok;
-  if constexpr (kSym) {
-    // the upper tiles row-major; xcd_b < 0: XCD x takes the x-th eighth of them
-    if (xcd_b < 0) {
-      const int x = blockIdx.x & 7, w = (blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-      const int T8 = sym_tiles<Tile::kCols>(trows, tcols);
-      const int lo = x * T8 / 8, hi = (x + 1) * T8 / 8;
-      t = __builtin_amdgcn_readfirstlane(lo + w);
-      ok = t < hi;
-    } else {
-      ok = true;
-    }
-    ok = ok && sym_tile<Tile::kCols>(t, trows, tcols, tr, tc);
-  } else if (xcd_b < 0) {
-    const int x = blockIdx.x & 7, w = (blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const int hx = x / kRegCols, qx = x % kRegCols;
-    const int r0 = hx * trows / kRegRows, r1 = (hx + 1) * trows / kRegRows;
-    const int c0 = qx * tcols / kRegCols, c1 = (qx + 1) * tcols / kRegCols;
-    const int cw = c1 - c0;
-    const int tt = __builtin_amdgcn_readfirstlane(w);
-    ok = tt < (r1 - r0) * cw;
-    tr = r0 + tt / cw;
-    tc = c0 + tt % cw;
-  } else {
-    ok = t < trows * tcols;
-    tr = t / tcols;
-    tc = t - tr * tcols;
-  }
-  if constexpr (std::is_same<Tile, SigmaTile<float>>::value) {
-    // fp32: the operand loads depend only on the filter and the tile, so they go out before the
-    // descriptor's scalar round trips (flags, parity, m, then the Σ pointer it selects) instead of
-    // behind them (≈ 0.3 µs of a 9 µs pass, tools/pass_lab.hip)
-    if (!ok) return;
-    const int f = A.f0 + fb;
-    // the patch test's record flags of both parities, issued with the operands (not a scalar round
-    // trip behind the descriptor's parity: that wait cost ≈ 0.4 µs of the pass)
-    const int rf0 = A.rec[f].flags, rf1 = A.rec[A.rec_stride + f].flags;
-    F32TileRegs g;
-    Tile::load_ops(g, A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.n, A.ldk,
-                   tr * Tile::kRows, tc * Tile::kCols, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    if (d.flags & kActive) {
-      SIG_STAMP(1);
-      const int kw = ((2 + ((d.flags & kJoseph) ? 4 : 2) * d.m + 3) / 4) * 4;
-      Tile::load_sig(g, A.sig[d.parity] + f * A.sig_stride, A.n, A.ld, tr * Tile::kRows,
-                     tc * Tile::kCols, lane);
-      // the fp32 patch (see k_patch_stage): the chain's fp64 Σ[U, U] over this tile's entries
-      // there, for the chunks that initialised a landmark (the pass's 1e7 − (1e7 − δ) loses δ)
-      const ChunkRec* rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
-      const int* pm = nullptr;
-      if ((d.parity ? rf1 : rf0) & kPendValid) {  // wave-uniform
-        const int R0 = tr * Tile::kRows, C0 = tc * Tile::kCols;
-        int* map = cmap[threadIdx.x >> 6];
-        map[lane] = kMaxU;
-        const int nu = rec->nu, u = rec->u[min(lane, kMaxU - 1)];
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        if (lane < nu && u >= R0 && u < R0 + 32) atomicMin(&map[u - R0], lane);
-        if (lane < nu && u >= C0 && u < C0 + 32) atomicMin(&map[32 + u - C0], lane);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        pm = map;
-      }
-      if constexpr (KB == 1)
-        Tile::finish(g, A.sig[d.parity ^ 1] + f * A.sig_stride, A.n, A.ld, kw,
-                     (d.flags & kFirst) != 0, A.q, tr * Tile::kRows, tc * Tile::kCols, lane, pm,
-                     rec);
-      else
-        Tile::finish2(g, A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.ldk,
-                      A.sig[d.parity ^ 1] + f * A.sig_stride, A.n, A.ld, kw,
-                      (d.flags & kFirst) != 0, A.q, tr * Tile::kRows, tc * Tile::kCols, lane, pm,
-                      rec);
-    }
-  } else if ((d.flags & kActive) && ok) {
-    SIG_STAMP(1);
-    const int f = A.f0 + fb;
-    // this filter's rank (Joseph: K·M and V·Kᵀ per marker); rows beyond are stale
-    const int kw = ((2 + ((d.flags & kJoseph) ? 4 : 2) * d.m + 3) / 4) * 4;
-    Tile::template run<KB>(A.sig[d.parity] + f * A.sig_stride, A.sig[d.parity ^ 1] + f * A.sig_stride,
-              A.kcat + f * A.km_stride, A.mcat + f * A.km_stride, A.n, A.ld, A.ldk, kw,
-              (d.flags & kFirst) != 0, A.q, tr * Tile::kRows, tc * Tile::kCols, lane,
-              tT[threadIdx.x >> 6]);
-  }
+  SIG_STAMP(0);
+  __shared__ int cmap[kPassWaves][64];  // per wave: the fp32 tile's patch map
+  __shared__ double tT[kPassWaves][kSym ? PassTile<double, WIDE>::kLds : 1];  // fp64: the mirror
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // The wave's filter and tile are sigma_grid_tile's. Two things only keep the scalar loads ahead
+  // of it as few as they were (each is a dependent round trip before the wave's first vector
+  // load; one more was + 0.5 % on the swarm's pass, profiles/r14/sigma_pass_grid/): the waves per
+  // workgroup are the kernel's own constant instead of a field loaded from G, and the workgroup's
+  // filter is resolved first, which brings the XCD-dealt grid's fields in with the first load.
+  SigmaGrid g = G;
+  g.wpb = kPassWaves;
+  int b;
+  if (sigma_grid_filter(g, blockIdx.x, blockIdx.y, b) < 0) return;
+  const SigmaTileAt at = sigma_grid_tile<Tile::kCols, kSym>(g, blockIdx.x, blockIdx.y, wave);
+  if (at.filter < 0) return;
+  const MsgDesc& d = A.desc[at.filter];
+  if constexpr (kSym)
+    pass_tile_f64<Tile, KB>(A, d, at.filter, at.tr, at.tc, lane, tT[wave]);
+  else
+    pass_tile_f32<KB>(A, d, at.filter, at.tr, at.tc, lane, cmap[wave]);
   SIG_STAMP(3);
 }
-
 
 // Right behind the Σ pass on its stream, for chunks that stage (kStageOut, either dtype): the
 // rebuild operands of the filter's chunk after next (StageRec), gathered from the Σ_out / x_out
 // just completed — off the chain's critical path, where the same gather at the chain's start cost
 // ≈ 10 µs of a 47 µs message (≈ 1 900 scattered lines through one CU). One workgroup per filter.
-// The fp32 patch this kernel also did until round 4 — the chain's fp64 Σ[U, U] (rec->Pend, rounded
-// once) over the pass's values, because the pass's 1e7 − (1e7 − δ) at a first sighting (the
-// reference's prior, slam.cpp:130) loses δ in fp32 — now happens in the pass's tiles
-// (SigmaTile<float>::finish), so Σ_out is already patched here; the patch branches below are off.
+// fp32: the pass's tiles have already written the chain's fp64 Σ[U, U] over their entries
+// (pass_tile_f32), so the Σ_out read here is the patched one, as the chain would gather it.
 template <typename T>
-__global__ __launch_bounds__(256) void k_patch_stage(PassArgs<T> A) {
-  // (the fp32 patch itself now happens in the Σ pass's tiles, SigmaTile<float>::finish: the
-  // staging below reads the patched Σ_out)
-  constexpr bool kPatch = false;
+__global__ __launch_bounds__(256) void k_stage(PassArgs<T> A) {
   const MsgDesc& d = A.desc[blockIdx.x];
   const int flags = d.flags;
-  if (!(flags & kActive)) return;
-  const bool stage = (flags & kStageOut) != 0;
-  if (!kPatch && !stage) return;
+  if (!(flags & kActive) || !(flags & kStageOut)) return;
   const int f = A.f0 + blockIdx.x;
   const int tid = threadIdx.x;
-  const ChunkRec* rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
-  // the chain wrote Pend only for chunks that initialised a landmark (k_chain: `pend`)
-  const bool patch = kPatch && (rec->flags & kPendValid);
-  if (!patch && !stage) return;
-  __shared__ int su[kMaxU];
-  __shared__ int sfirst[kMaxU];           // position is its index's first in this chunk's U
-  __shared__ double spend[kMaxU][kMaxU + 1];
-  __shared__ int sgu[kStW], sgp[kStW];    // staged chain's U and U' (columns)
-  __shared__ int sgfu[kStW], sgfp[kStW];  // their first positions in this chunk's U (patched), −1
-  // ---- one global round trip: the record's block and U, the staged chunks' ids ----
-  constexpr int kPer = (kMaxU * kMaxU + 255) / 256;
-  double pv[kPer];
-  if (patch) {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = min(tid + 256 * i, kMaxU * kMaxU - 1);
-      pv[i] = rec->Pend[e / kMaxU][e % kMaxU];
-    }
-  }
-  const int nu = rec->nu;
-  const int myu = rec->u[min(tid, kMaxU - 1)];
-  // stage threads: a = tid (U of the chunk after next) or tid − 64 (U', the next chunk's)
+  __shared__ int sgu[kStW], sgp[kStW];  // staged chain's U and U' (columns)
+  // ---- one global round trip: the staged chunks' ids ----
+  // threads 0 … 35: a = tid (U of the chunk after next); 64 … 99: a = tid − 64 (U', the next chunk's)
   const bool isp = tid >= 64;
   const int sa = isp ? tid - 64 : tid;
   const int sm = isp ? d.stg_pm : d.stg_m;
   const int sid = (isp ? d.stg_pids : d.stg_ids)[min(max(sa - 3, 0) >> 1, kMaxChunk - 1)];
-  if (tid < kMaxU) su[tid] = myu;
-  if (patch) {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = tid + 256 * i;
-      if (e < kMaxU * kMaxU) spend[e / kMaxU][e % kMaxU] = pv[i];
-    }
-  }
-  __syncthreads();
-  // ---- first positions: every lane takes all of U into registers (one LDS wait) ----
-  int uall[kMaxU];
-#pragma unroll
-  for (int k = 0; k < kMaxU; ++k) uall[k] = su[k];
-  if (tid < kMaxU) {
-    bool fp = tid < nu;
-#pragma unroll
-    for (int k = 0; k < kMaxU; ++k) fp = fp && !(k < tid && uall[k] == myu);
-    sfirst[tid] = fp;
-  }
-  if (stage && sa < kStW && (tid < kStW || (isp && tid < 64 + kStW))) {
+  if (sa < kStW && (tid < kStW || (isp && tid < 64 + kStW))) {
     int col = 0;
     if (sa < 3) col = sa;
     else if (sa < 3 + 2 * sm && sa < kMaxU)
       // k_chain's A0 mapping: marker c → 3 + 2·id (+1), a bad id → slot 0's, padding → 0
       col = (sid < 0 || sid >= A.N ? 3 : 3 + 2 * sid) + ((sa - 3) & 1);
-    int fpos = -1;  // the first position of col in this chunk's U = its patched entry
-    if (patch) {
-#pragma unroll
-      for (int k = kMaxU - 1; k >= 0; --k) fpos = (k < nu && uall[k] == col) ? k : fpos;
-    }
     (isp ? sgp : sgu)[sa] = col;
-    (isp ? sgfp : sgfu)[sa] = fpos;
   }
   __syncthreads();
-  T* S = A.sig[d.parity ^ 1] + f * A.sig_stride;
-  if (patch) {
-#pragma unroll
-    for (int i = 0; i < kPer; ++i) {
-      const int e = tid + 256 * i, a = e / kMaxU, b = e % kMaxU;
-      if (e < kMaxU * kMaxU && sfirst[a] && sfirst[b])
-        S[static_cast<size_t>(su[a]) * A.ld + su[b]] = static_cast<T>(pv[i]);
-    }
-  }
-  if (!stage) return;
   // ---- stage: the chunk after next's rebuild operands (the second global round trip) ----
+  const T* S = A.sig[d.parity ^ 1] + f * A.sig_stride;
   const double* xo = A.x[d.parity ^ 1] + f * A.x_stride;
   StageRec<T>* sg = A.stage + static_cast<size_t>(d.parity) * A.rec_stride + f;
-  // Σ_out[r][c] as the chain would read it after the patch (the load of a patched entry races
-  // the scatter above and is discarded)
-  auto val = [&](int r, int fr, int c, int fc) -> T {
-    const T g = S[static_cast<size_t>(r) * A.ld + c];
-    return (patch && fr >= 0 && fc >= 0) ? static_cast<T>(spend[fr][fc]) : g;
-  };
+  auto val = [&](int r, int c) -> T { return S[static_cast<size_t>(r) * A.ld + c]; };
   // The three blocks by image position (RebuildImage: the chain's LDS layout), entry e = row·36 +
   // column of each: D and R rows a over U, C rows k over U' with a along the row (the transposed
   // store the chain did). Loads unconditional (clamped), zeros selected after: a ≥ |U|, b ≥ |U|,
@@ -565,17 +448,16 @@ __global__ __launch_bounds__(256) void k_patch_stage(PassArgs<T> A) {
     const int e = min(tid + 256 * i, kStW * kStW - 1);
     const int r = e / kStW, c = e % kStW;
     const int a = min(r, kMaxU - 1), b = min(c, kMaxU - 1);
-    const T vd = val(sgu[a], sgfu[a], sgu[b], sgfu[b]);
-    const T vr = val(sgu[a], sgfu[a], sgp[b], sgfp[b]);
-    const T vc = val(sgp[a], sgfp[a], sgu[b], sgfu[b]);  // C[k = r][a = c]
+    const T vd = val(sgu[a], sgu[b]);
+    const T vr = val(sgu[a], sgp[b]);
+    const T vc = val(sgp[a], sgu[b]);  // C[k = r][a = c]
     od[i] = r < gnu && c < gnu ? vd : T(0);
     orr[i] = r < gnu && c < gnp ? vr : T(0);
     oc[i] = r < gnp && c < gnu ? vc : T(0);
   }
-  const int t = min(tid, kMaxU - 1);
-  const int z = sgfu[0];  // position 0 of U is the pose θ column
-  const T r0u = val(0, z, sgu[t], sgfu[t]), c0u = val(sgu[t], sgfu[t], 0, z);
-  const T r0p = val(0, z, sgp[t], sgfp[t]), c0p = val(sgp[t], sgfp[t], 0, z);
+  const int t = min(tid, kMaxU - 1);  // (row / column 0: the pose θ)
+  const T r0u = val(0, sgu[t]), c0u = val(sgu[t], 0);
+  const T r0p = val(0, sgp[t]), c0p = val(sgp[t], 0);
   const double xg = xo[sgu[t]];
   if (tid < kStW) {
     sg->r0u[tid] = static_cast<double>(r0u);
@@ -601,37 +483,24 @@ __global__ __launch_bounds__(256) void k_patch_stage(PassArgs<T> A) {
 __global__ void k_sigma_epoch(unsigned* sync, unsigned epoch) {
   if (threadIdx.x == 0) epoch_store(sync + kSyncSigma, epoch);
 }
+// The pass with the WIDE or the narrow tile, on that tile's grid (fp64: the symmetric one).
+template <typename T, bool WIDE>
+static void launch_pass_tiles(const PassArgs<T>& a, int nf, hipStream_t s, hipEvent_t e0,
+                              hipEvent_t e1) {
+  using Tile = PassTile<T, WIDE>;
+  const SigmaGrid g = sigma_grid(a.n, nf, Tile::kRows, Tile::kCols, sizeof(T) == 8, kPassWaves);
+  launch(a.joseph ? k_sigma_pass<T, WIDE, 2> : k_sigma_pass<T, WIDE, 1>, dim3(g.grid_x, g.grid_y),
+         dim3(64 * kPassWaves), s, e0, e1, a, g);
+}
 template <typename T>
 hipError_t launch_sigma_pass(const PassArgs<T>& a, int nf, bool publish, bool stage, hipStream_t s,
                              hipEvent_t e0, hipEvent_t e1) {
-  constexpr int wpb = 4;  // waves per workgroup
-  // the tiles per filter: all of them, or (fp64, symmetric) those on or above the diagonal
-  auto tiles = [](int trows, int tcols, auto tile) {
-    using Tile = decltype(tile);
-    return sizeof(T) == 8 ? sym_tiles<Tile::kCols>(trows, tcols) : trows * tcols;
-  };
-  if (nf >= 16) {  // XCD-aware 1-D grid (see k_sigma_pass), wide fp64 tiles
-    using Tile = PassTile<T, true>;
-    const int trows = (a.n + Tile::kRows - 1) / Tile::kRows;
-    const int tcols = (a.n + Tile::kCols - 1) / Tile::kCols;
-    const int per_filter = (tiles(trows, tcols, Tile{}) + wpb - 1) / wpb;
-    const dim3 grid(8 * ((nf + 7) / 8) * per_filter);
-    launch(a.joseph ? k_sigma_pass<T, true, 2> : k_sigma_pass<T, true, 1>, grid, dim3(64 * wpb), s, e0, e1, a, tcols, per_filter, nf);
-  } else {
-    using Tile = PassTile<T, false>;
-    const int trows = (a.n + Tile::kRows - 1) / Tile::kRows;
-    const int tcols = (a.n + Tile::kCols - 1) / Tile::kCols;
-    if (trows >= 2 * kRegRows && tcols >= 2 * kRegCols) {  // XCD regions (k_sigma_pass)
-      const int per_x = sizeof(T) == 8 ? (tiles(trows, tcols, Tile{}) + 7) / 8 : region_tiles(trows, tcols);
-      const dim3 grid(8 * ((per_x + wpb - 1) / wpb), nf);
-      launch(a.joseph ? k_sigma_pass<T, false, 2> : k_sigma_pass<T, false, 1>, grid, dim3(64 * wpb), s, e0, e1, a, tcols, -1, nf);
-    } else {
-      const int per_filter = (tiles(trows, tcols, Tile{}) + wpb - 1) / wpb;
-      const dim3 grid(per_filter, nf);
-      launch(a.joseph ? k_sigma_pass<T, false, 2> : k_sigma_pass<T, false, 1>, grid, dim3(64 * wpb), s, e0, e1, a, tcols, 0, nf);
-    }
-  }
-  if (stage) hipLaunchKernelGGL(k_patch_stage<T>, dim3(nf), dim3(256), 0, s, a);
+  // the swarms' XCD-dealt grid goes with the wide fp64 tile
+  if (nf >= kGridXcdFilters)
+    launch_pass_tiles<T, true>(a, nf, s, e0, e1);
+  else
+    launch_pass_tiles<T, false>(a, nf, s, e0, e1);
+  if (stage) hipLaunchKernelGGL(k_stage<T>, dim3(nf), dim3(256), 0, s, a);
   // the pass's epoch (otherwise published by the next chunk's factor kernel, PassArgs::pub_sigma)
   if (publish && a.polls)
     hipLaunchKernelGGL(k_sigma_epoch, dim3(1), dim3(64), 0, s, a.sync, a.seq + 1u);
@@ -643,3 +512,4 @@ template hipError_t launch_sigma_pass<float>(const PassArgs<float>&, int, bool, 
                                              hipEvent_t, hipEvent_t);
 
 }  // namespace ekfslam
+

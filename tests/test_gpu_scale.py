@@ -237,8 +237,8 @@ def test_n1024_fp32_populated_against_oracle(n1024, env, monkeypatch):
 
 @pytest.mark.parametrize("devsync", ["1", "0"], ids=["devsync", "events"])
 def test_n1024_fp32_staged_rebuild_bit_identical(n1024, devsync, monkeypatch):
-    """configs[2] fp32 (the block patch k_patch_stage writes over the Σ pass's U × U entries, and
-    the stage must see it): 12 circle messages from the survey's state with the rebuild operands
+    """configs[2] fp32 (the block patch the Σ pass's tiles write over their U × U entries, and
+    k_stage must see it): 12 circle messages from the survey's state with the rebuild operands
     staged behind the Σ passes and gathered by the chains (EKF_STAGE=0): bit-identical."""
     sc, odom, ws = n1024
     w = sc.n_warm

@@ -4,7 +4,9 @@ n = 3 + 2N. Every pipeline size the rest of the suite runs has n mod 32 in {3, 7
 give n mod 32 = 31, 1, 15, 17 (a last 32x32 / 16x16 / 32x64 tile row and column 31, 1, 15 or 17
 elements wide, ld = n + 1 or n rounded up, the buffer-descriptor range check in place of masks),
 with N = 64 (n = 131, residue 3) as the control, on populated maps: every landmark is initialised,
-so the last rows and columns are live. k_assoc_msg puts 64 slots in a workgroup: N = 63, 65, 127,
+so the last rows and columns are live. N = 110 (n = 223, 7 × 7 tiles of 32 × 32) is the last size
+on the Σ pass's plain grid, N = 111 (n = 225, 8 × 8 tiles, the last ones one element wide) the
+first on its XCD-region grid (sigma_grid.hpp). k_assoc_msg puts 64 slots in a workgroup: N = 63, 65, 127,
 129 leave 63, 1, 63, 1 live lanes in the last one, with a commit on the very last slot.
 
 Bounds are test_gpu_scale.py's, whose docstring derives them for exactly this kind of surveyed map
@@ -25,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 F64_TOL = es.ASSOC_TOL   # 1e-8 / 5e-8 / 1e-7, test_gpu_scale.py's populated-map bounds
 F32_TOL = es.F32_TOL     # 5e-6 / 1e-5 / 5e-5, its N = 256 survey test's
-KNOWN_SIZES = [14, 15, 31, 63, 64, 70, 71, 78, 79, 94, 95, 127]
+KNOWN_SIZES = [14, 15, 31, 63, 64, 70, 71, 78, 79, 94, 95, 110, 111, 127]
 WIDE_SIZES = [15, 63, 78, 94, 95]
 ASSOC_SIZES = [63, 65, 127, 129]
 ERRORS = {}

@@ -2,7 +2,7 @@
 
 A kLook chain rebuilds its |U| × |U| block from three blocks over U (its own index set) and U' (the
 previous chunk's): D = Σ[U, U], R = Σ[U, U'] and C = Σ[U', U] (kept transposed in LDS), zero-padded
-to 36 columns for the MFMA k loop. k_patch_stage writes them two chunks ahead in the layout of the
+to 36 columns for the MFMA k loop. k_stage writes them two chunks ahead in the layout of the
 chain's LDS arrays (RebuildImage) and the chain copies them in; the first two chunks of a call and
 EKF_STAGE=0 chains gather the same values themselves. What the hand-over can get wrong: |U| ≠ |U'|
 (the zero columns k ≥ |U'|), the padding, the transposed C, a previous chunk without a predict (the second

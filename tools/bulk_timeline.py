@@ -1,5 +1,5 @@
 """Dev tool: the bulk stream's loop per chunk from a rocprofv3 kernel trace (rocpd database):
-k_factors / k_sigma_pass / k_patch_stage start, end and the gaps between them, steady state of the
+k_factors / k_sigma_pass / k_stage start, end and the gaps between them, steady state of the
 first chain launch of > 100 chunks (median over its chunks).  python tools/bulk_timeline.py <run_results.db> [launch]"""
 import sqlite3
 import sys
@@ -8,7 +8,9 @@ import numpy as np
 
 c = sqlite3.connect(sys.argv[1])
 rows = c.execute("select name, start, [end] from kernels order by start").fetchall()
-names = {"k_chain": "chain", "k_factors": "fac", "k_sigma_pass": "pass", "k_patch_stage": "stage"}
+# (k_patch_stage: k_stage's name in traces from before round 14)
+names = {"k_chain": "chain", "k_factors": "fac", "k_sigma_pass": "pass", "k_stage": "stage",
+         "k_patch_stage": "stage"}
 ev = []
 for n, s, e in rows:
     for k, v in names.items():

@@ -12,7 +12,7 @@
 using namespace ekfslam;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP %s @%d\n", hipGetErrorString(e_), __LINE__); exit(1);} } while (0)
 
-// the product's region mapping (k_sigma_pass, xcd_b = −1) for WPB waves per workgroup. MODE bits:
+// the product's region mapping (sigma_grid.hpp, kGridRegions) for WPB waves per workgroup. MODE bits:
 // 1 Σ buffers chosen by the descriptor's parity (as the product: every load waits for it),
 // 2 no MFMA (one VALU product keeps the operand loads live), 4 constant operands (no operand loads),
 // 8 issue priority 2 once the MFMAs are done, 16 Σ_in loads issued before the operand loads
@@ -278,7 +278,9 @@ __global__ __launch_bounds__(64 * WPB) void k_lab_band(PassArgs<float> A, int tc
   const int tr = t / tcols, tc = t - tr * tcols;
   const int kw = ((2 + 2 * d.m + 3) / 4) * 4;
   F32TileRegs g;
-  Tile::load(g, A.sig[0], A.kcat, A.mcat, A.n, A.ld, A.ldk, tr * 32, tc * 32, lane);
+  Tile::load_ops(g, A.kcat, A.mcat, A.n, A.ldk, tr * 32, tc * 32, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  Tile::load_sig(g, A.sig[0], A.n, A.ld, tr * 32, tc * 32, lane);
   Tile::finish(g, A.sig[1], A.n, A.ld, kw, (d.flags & kFirst) != 0, A.q, tr * 32, tc * 32, lane);
 }
 template <int WPB>
@@ -569,9 +571,9 @@ int main(int argc, char** argv) {
   const double bytes = 2.0 * n * n * 4;
   std::vector<float> ref(stride), out(stride);
   auto prod = [&](hipStream_t st) {
-    const int trows = (n + 31) / 32, tcols = trows;
-    hipLaunchKernelGGL((k_sigma_pass<float, false, 1>), dim3(8 * ((region_tiles(trows, tcols) + 3) / 4), 1),
-                       dim3(256), 0, st, a, tcols, -1, 1);
+    const SigmaGrid g = sigma_grid(n, 1, 32, 32, false, kPassWaves);
+    hipLaunchKernelGGL((k_sigma_pass<float, false, 1>), dim3(g.grid_x, g.grid_y), dim3(64 * kPassWaves), 0,
+                       st, a, g);
   };
   struct V { const char* name; void (*fn)(const PassArgs<float>&, hipStream_t); };
   auto time_it = [&](const char* name, auto&& fn) {
