@@ -7,6 +7,7 @@
 #include "ekf.h"
 #include "ekf_device.hpp"
 #include "ekf_launch.hpp"
+#include "landmarks.h"
 
 namespace ekfslam {
 
@@ -46,6 +47,46 @@ int replay_markers(ekf_t h, int device, int T, int m_max, const int* d_counts,
 int replay_markers_resident(ekf_t h, int device, int T, int m_max, const int* d_counts,
                             const double* d_markers, const double* odom, hipEvent_t ready,
                             hipEvent_t consumed);
+
+// The two above with the messages' odometry d_odom[T][F][3] already on the device instead of on
+// the host (ekf_sim_run_lidar: the simulator's own buffer, read by the planner / the replay kernel
+// in place, so `planned` / `consumed` frees it as it frees the markers). Nothing is uploaded.
+int replay_markers_device(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                          const double* d_markers, const double* d_odom, hipEvent_t ready,
+                          hipEvent_t planned);
+int replay_markers_resident_device(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                                   const double* d_markers, const double* d_odom,
+                                   hipEvent_t ready, hipEvent_t consumed);
+
+// The front-end side of ekf_sim_run_lidar (lm_api.cpp). lm_lidar_check: EKF_E_ARG for what the
+// handle cannot take — another device, n_scans outside [1, max_scans], n_beams outside
+// [2, max_beams], max_markers outside [1, 64], an invalid scan configuration (lm_simulate's
+// rules; scan0 is not looked at) — and touches nothing.
+int lm_lidar_check(lm_t h, int device, int n_scans, int n_beams, int max_markers,
+                   const lm_scan_config* cfg);
+// What a run hands the front-end: the simulator's device buffers and its noise shard.
+struct LidarRun {
+  const double* d_truth;  // [T·F][3]
+  const double* d_lm;     // [F][L][2]
+  int T, F, L, n_beams, max_markers;
+  unsigned long long seed;  // cfg.seed + f0
+  long long msg0;
+  double radius, threshold;
+  const lm_scan_config* scan;
+};
+// What the replay behind it reads: the handle's counts and markers (lm_marker rows, stride 4) and
+// the events of lm_replay_into (the detect's, and the one the filter records once it has planned).
+struct LidarFeed {
+  const int* d_counts;
+  const double* d_markers;
+  hipEvent_t ready, planned;
+};
+// On the handle's stream, behind `after` (the simulation): k_lidar_scan_swarm into the range
+// buffer, then the detect, as lm_simulate + lm_detect_device leave them (scans resident, markers on
+// the device). Arguments as checked by lm_lidar_check.
+int lm_lidar_enqueue(lm_t h, const LidarRun& run, hipEvent_t after, LidarFeed* out);
+// A replay has been enqueued on feed.planned: the handle's next detect waits for it.
+void lm_lidar_planned(lm_t h);
 
 // ekf_eval with the truth already on the handle's device (ekf_sim_eval): filter f's true pose at
 // d_pose[f·pose_stride], its map d_lm[F][n_map][2] (nullable with n_map = 0), frame[3] nullable.

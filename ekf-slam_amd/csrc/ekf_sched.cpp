@@ -807,6 +807,25 @@ int replay_markers_resident(ekf_t h, int device, int T, int m_max, const int* d_
                          ready, consumed);
 }
 
+int replay_markers_device(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                          const double* d_markers, const double* d_odom, hipEvent_t ready,
+                          hipEvent_t planned) {
+  if (!h || device != h->cfg.device || T < 1 || m_max < 1 || m_max > kMaxAssoc || !d_counts ||
+      !d_markers || !d_odom || !device_assoc_supported(h))
+    return EKF_E_ARG;
+  return replay_device_assoc(h, T, m_max, d_counts, d_markers, 4, d_odom, nullptr, ready, planned);
+}
+
+int replay_markers_resident_device(ekf_t h, int device, int T, int m_max, const int* d_counts,
+                                   const double* d_markers, const double* d_odom,
+                                   hipEvent_t ready, hipEvent_t consumed) {
+  if (!h || device != h->cfg.device || T < 1 || m_max < 1 || m_max > kMaxAssoc || !d_counts ||
+      !d_markers || !d_odom || !h->resident)
+    return EKF_E_ARG;
+  return replay_resident(h, 1, T, m_max, d_counts, nullptr, nullptr, d_markers, 4, d_odom, nullptr,
+                         ready, consumed);
+}
+
 int handle_info(ekf_t h, HandleInfo* out) {
   if (!h || !out) return EKF_E_ARG;
   if (int rc = flush(h)) return rc;

@@ -3,9 +3,11 @@
 // (nusim/src/nusim.cpp:559-710) over lidar_kernels.hip whose scans it can detect on in place.
 // lm_detect_device leaves the markers on the device, and lm_replay_into hands them to a filter
 // handle's device planner (k_plan_assoc) without a host hop; lm_replay_resident to a resident
-// handle's replay kernel, which reads them in place.
+// handle's replay kernel, which reads them in place. The simulator (sim_api.cpp) drives the same
+// chain from its own device buffers through lm_lidar_enqueue: laser, detect, markers left in place.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <new>
 
 #include "ekf.h"
@@ -120,7 +122,68 @@ int upload_scans(lm_t h, int S, int B, const float* ranges, const double* amin,
   return EKF_OK;
 }
 
+// lm_simulate's rules for a scan configuration (scan0 aside)
+bool scan_config_ok(const lm_scan_config* cfg) {
+  return cfg && cfg->sigma >= 0.0 && cfg->range_min <= cfg->range_max;
+}
+
 }  // namespace
+
+// ---- ekf_sim_run_lidar's hook (ekf_internal.hpp) -------------------------------------------------
+namespace ekfslam {
+
+int lm_lidar_check(lm_t h, int device, int n_scans, int n_beams, int max_markers,
+                   const lm_scan_config* cfg) {
+  if (!h || device != h->device || n_scans < 1 || n_scans > h->max_scans || n_beams < 2 ||
+      n_beams > h->max_beams || max_markers < 1 || max_markers > 64 || !scan_config_ok(cfg))
+    return EKF_E_ARG;
+  return EKF_OK;
+}
+
+int lm_lidar_enqueue(lm_t h, const LidarRun& run, hipEvent_t after, LidarFeed* out) {
+  const int S = run.T * run.F;
+  const hipStream_t st = h->stream.get();
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  h->res_scans = h->res_beams = 0;
+  lmk::SwarmScanArgs a{};
+  a.poses = run.d_truth;
+  a.lm = run.d_lm;
+  a.ranges = h->d_ranges.get();
+  a.angle_min = h->d_amin.get();
+  a.angle_inc = h->d_ainc.get();
+  a.n_scans = S;
+  a.n_beams = run.n_beams;
+  a.n_filters = run.F;
+  a.n_map = run.L;
+  a.seed = run.seed;
+  a.msg0 = run.msg0;
+  a.radius = run.radius;
+  a.arena_w = run.scan->arena_w;
+  a.arena_h = run.scan->arena_h;
+  a.range_min = run.scan->range_min;
+  a.range_max = run.scan->range_max;
+  a.sigma = run.scan->sigma;
+  const char* from = std::getenv("EKF_LIDAR_CULL_FROM");  // (measurements only: same bits)
+  a.cull_from = from ? std::atoi(from) : lmk::kCullFromMap;
+  if (hipStreamWaitEvent(st, after, 0) != hipSuccess ||
+      hipEventRecord(h->s0.get(), st) != hipSuccess ||
+      lmk::launch_scan_swarm(a, st) != hipSuccess || hipEventRecord(h->s1.get(), st) != hipSuccess)
+    return EKF_E_HIP;
+  h->sim_timed = true;
+  h->res_scans = S;
+  h->res_beams = run.n_beams;
+  if (int rc = enqueue_detect(h, S, run.n_beams, run.threshold, run.max_markers)) return rc;
+  if (hipEventRecord(h->e_det.get(), st) != hipSuccess) return EKF_E_HIP;
+  h->dev_scans = S;
+  h->dev_cap = run.max_markers;
+  *out = LidarFeed{h->d_counts.get(), reinterpret_cast<const double*>(h->d_markers.get()),
+                   h->e_det.get(), h->e_planned.get()};
+  return EKF_OK;
+}
+
+void lm_lidar_planned(lm_t h) { h->planner_reads = true; }
+
+}  // namespace ekfslam
 
 extern "C" {
 
@@ -187,8 +250,7 @@ void lm_scan_config_default(lm_scan_config* c) {
 int lm_simulate(lm_t h, int S, int B, const double* poses, int G, int C, const double* circles,
                 const int* scene, const lm_scan_config* cfg, float* ranges_out) {
   if (!h || S <= 0 || S > h->max_scans || B < 2 || B > h->max_beams || !poses || G < 1 || C < 0 ||
-      C > LM_MAX_CIRCLES || (C > 0 && !circles) || !cfg || !(cfg->sigma >= 0.0) ||
-      !(cfg->range_min <= cfg->range_max) || cfg->scan0 < 0)
+      C > LM_MAX_CIRCLES || (C > 0 && !circles) || !scan_config_ok(cfg) || cfg->scan0 < 0)
     return EKF_E_ARG;
   for (int s = 0; scene && s < S; ++s)
     if (scene[s] < 0 || scene[s] >= G) return EKF_E_ARG;
@@ -320,10 +382,20 @@ int lm_replay_resident(lm_t h, ekf_t e, int T, const double* odom) {
   return rc;
 }
 
+int lm_fetch_ranges(lm_t h, float* out) {
+  if (!h || !out || h->res_scans <= 0) return EKF_E_ARG;
+  if (hipSetDevice(h->device) != hipSuccess) return EKF_E_HIP;
+  const size_t n = static_cast<size_t>(h->res_scans) * h->res_beams;
+  if (hipMemcpyAsync(out, h->d_ranges.get(), sizeof(float) * n, hipMemcpyDeviceToHost,
+                     h->stream.get()) != hipSuccess)
+    return EKF_E_HIP;
+  return hipStreamSynchronize(h->stream.get()) == hipSuccess ? EKF_OK : EKF_E_HIP;
+}
+
 int lm_last_simulate_us(lm_t h, double* us) {
   if (!h || !us || !h->sim_timed) return EKF_E_ARG;
   float ms = 0.0f;
-  // (lm_simulate may have left the kernel in flight)
+  // (lm_simulate and ekf_sim_run_lidar may have left the kernel in flight)
   if (hipEventSynchronize(h->s1.get()) != hipSuccess ||
       hipEventElapsedTime(&ms, h->s0.get(), h->s1.get()) != hipSuccess)
     return EKF_E_HIP;

@@ -55,4 +55,25 @@ struct ScanArgs {
 };
 hipError_t launch_scan(const ScanArgs& a, hipStream_t st);
 
+// ekf_sim_run_lidar's kernel (k_lidar_scan_swarm): a simulator run scanned where it lies. Scan
+// s = t·F + f is message t of filter f: its pose poses[s], its scene filter f's map with one
+// radius, its noise seed + f with beam b on draw (msg0 + t)·B + b.
+struct SwarmScanArgs {
+  const double* poses;  // [T·F][3] body (θ, x, y): the simulator's truth buffer
+  const double* lm;     // [F][L][2] cylinder centres: the simulator's maps
+  float* ranges;        // [T·F][B] out
+  double* angle_min;    // [T·F] out: 0
+  double* angle_inc;    // [T·F] out: float32(2π/B)
+  int n_scans, n_beams, n_filters, n_map;  // n_scans = T·F; 1 ≤ n_map ≤ LM_MAX_CIRCLES
+  unsigned long long seed;                 // the simulator's seed + f0
+  long long msg0;                          // the run's first message
+  double radius, arena_w, arena_h, range_min, range_max, sigma;
+  int cull_from;  // maps of fewer cylinders are staged whole (kCullFromMap)
+};
+// The smallest map the swarm kernel culls. Below it the cull's own cost (a second barrier, the
+// ballot and the LDS atomic) is not earned back: DESIGN.md has the measurement it was read from.
+// EKF_LIDAR_CULL_FROM overrides it for that measurement (tools/lidar_mc_bench.py); same bits.
+constexpr int kCullFromMap = 32;
+hipError_t launch_scan_swarm(const SwarmScanArgs& a, hipStream_t st);
+
 }  // namespace lmk

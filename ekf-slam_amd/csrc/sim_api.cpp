@@ -8,9 +8,12 @@
 // plans on the GPU — no host round trip at all (EKF_SIM_PARALLEL=0 keeps the sequential kernel).
 // ekf_sim_run_assoc always simulates in the parallel form and hands the marker arrays, ids ignored,
 // to the device-input association replay of the handle's path.
+// ekf_sim_run_lidar simulates likewise, then has a landmark front-end handle scan the truth poses
+// with the laser kernel and detect on the scans (lm_api.cpp's hook), and replays those markers.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -228,6 +231,50 @@ int run_assoc(ekf_sim* s, int T, const double* wheel_cmd) {
   return hipEventRecord(s->ev_done[b].get(), rs) == hipSuccess ? EKF_OK : EKF_E_HIP;
 }
 
+static_assert(kSimMaxMap <= LM_MAX_CIRCLES, "a simulator map is one LDS-resident laser scene");
+
+// ekf_sim_run_lidar: the same simulation; then on the front-end's stream, behind ev_sim, the laser
+// over the truth buffer and the maps and the detect over its scans; then the association replay of
+// the handle's path over the front-end's markers and this run's odometry buffer, behind the
+// detect's event. The replay's stream (as run_assoc's) reads the odometry; the laser's read of the
+// truth buffer is ahead of it in that chain (scan → detect → e_det → replay), so ev_done[b] on the
+// replay's stream covers both.
+int run_lidar(ekf_sim* s, lm_t lm, int T, const double* wheel_cmd,
+              const ekf_sim_lidar_config* cfg) {
+  const int b = s->buf;
+  s->buf ^= 1;
+  const long long msg0 = s->msg;
+  if (int rc = simulate_parallel(s, T, wheel_cmd, nullptr, b)) return rc;
+  const auto& k = s->run.mk[b];
+  LidarRun run{};
+  run.d_truth = k.truth.get();
+  run.d_lm = s->lm.get();
+  run.T = T;
+  run.F = s->info.F;
+  run.L = s->L;
+  run.n_beams = cfg->n_beams;
+  run.max_markers = cfg->max_markers;
+  run.seed = cfg->scan.seed + static_cast<unsigned long long>(s->cfg.f0);
+  run.msg0 = msg0;
+  run.radius = cfg->obstacle_radius;
+  run.threshold = cfg->threshold;
+  run.scan = &cfg->scan;
+  LidarFeed feed{};
+  if (int rc = lm_lidar_enqueue(lm, run, s->ev_sim.get(), &feed)) return rc;
+  const int dev = s->info.device, M = cfg->max_markers;
+  const int rc =
+      s->info.resident
+          ? replay_markers_resident_device(s->h, dev, T, M, feed.d_counts, feed.d_markers,
+                                           k.odomF.get(), feed.ready, feed.planned)
+          : replay_markers_device(s->h, dev, T, M, feed.d_counts, feed.d_markers, k.odomF.get(),
+                                  feed.ready, feed.planned);
+  // (an argument error comes back before anything is enqueued; past that the planner may be)
+  if (rc != EKF_E_ARG) lm_lidar_planned(lm);
+  if (rc) return rc;
+  const hipStream_t rs = s->info.resident || s->info.serial ? s->info.stream : s->info.bulk;
+  return hipEventRecord(s->ev_done[b].get(), rs) == hipSuccess ? EKF_OK : EKF_E_HIP;
+}
+
 }  // namespace
 
 extern "C" {
@@ -414,6 +461,38 @@ int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd) {
   s->assoc = true;
   if (int rc = reserve(s, T)) return rc;
   return run_assoc(s, T, wheel_cmd);
+}
+
+void ekf_sim_lidar_config_default(ekf_sim_lidar_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->n_beams = 360;
+  c->max_markers = 32;
+  c->threshold = 0.2;
+  c->obstacle_radius = 0.038;
+  lm_scan_config_default(&c->scan);
+}
+
+int ekf_sim_run_lidar(ekf_sim_t s, lm_t lm, int T, const double* wheel_cmd,
+                      const ekf_sim_lidar_config* cfg) {
+  if (!s || !lm || !cfg || T < 0 || (T > 0 && !wheel_cmd) || !(cfg->obstacle_radius >= 0.0))
+    return EKF_E_ARG;
+  // what the front-end or the replay underneath would refuse, before the simulator moves (T = 0
+  // asks for no scan: the handle's limits are checked with one)
+  const long long S = static_cast<long long>(T) * s->info.F;
+  if (S > INT_MAX) return EKF_E_ARG;
+  if (int rc = lm_lidar_check(lm, s->info.device, T > 0 ? static_cast<int>(S) : 1, cfg->n_beams,
+                              cfg->max_markers, &cfg->scan))
+    return rc;
+  int route = EKF_ASSOC_MARKER;
+  if (int rc = ekf_get_assoc_route(s->h, &route)) return rc;
+  if (!s->info.resident && route == EKF_ASSOC_MARKER) return EKF_E_ARG;
+  if (T == 0) return EKF_OK;
+  if (int rc = handle_info(s->h, &s->info)) return rc;  // host-planned work first, bulk joined
+  hipSetDevice(s->info.device);
+  s->assoc = true;  // both marker buffers: the replay reads this run's odometry from its own
+  if (int rc = reserve(s, T)) return rc;
+  return run_lidar(s, lm, T, wheel_cmd, cfg);
 }
 
 int ekf_sim_markers(ekf_sim_t s, int* counts, int* ids, int* actions, double* rel_xy) {

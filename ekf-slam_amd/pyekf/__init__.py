@@ -51,14 +51,16 @@ EXPORTS = [
     "ekf_sim_markers", "ekf_sim_poses",
     "ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval",
     "ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match",
+    "ekf_sim_lidar_config_default", "ekf_sim_run_lidar", "lm_fetch_ranges",
 ]
 TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear",
                  "slam_replay_trace")
 # what a library built from an earlier commit (EKF_LIB, the A/B tools) may lack
 EVAL_EXPORTS = ("ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval")
 MATCH_EXPORTS = ("ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match")
+LIDAR_EXPORTS = ("ekf_sim_lidar_config_default", "ekf_sim_run_lidar", "lm_fetch_ranges")
 LATER_EXPORTS = (TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident") + EVAL_EXPORTS +
-                 MATCH_EXPORTS + ("ekf_chain_path_counts",))
+                 MATCH_EXPORTS + ("ekf_chain_path_counts",) + LIDAR_EXPORTS)
 EKF_MATCH_MAX_MAP = 1024
 EKF_EVAL_POSE_NOT_PD, EKF_EVAL_LM_NOT_PD = 1, 2
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
@@ -84,6 +86,12 @@ class ScanConfig(C.Structure):
     _fields_ = [("seed", C.c_ulonglong), ("scan0", C.c_longlong),
                 ("arena_w", C.c_double), ("arena_h", C.c_double),
                 ("range_min", C.c_double), ("range_max", C.c_double), ("sigma", C.c_double)]
+
+
+class LidarConfig(C.Structure):
+    """ekf_sim_lidar_config (include/ekf_sim.h)."""
+    _fields_ = [("n_beams", C.c_int), ("max_markers", C.c_int), ("threshold", C.c_double),
+                ("obstacle_radius", C.c_double), ("scan", ScanConfig)]
 
 
 class TraceRec(C.Structure):
@@ -240,6 +248,9 @@ def lib():
             "ekf_eval_match": (_i, [_vp, _vp, _vp, _i, _vp, _d, _vp, _vp, _vp]),
             "ekf_sim_run_assoc": (_i, [_vp, _i, _vp]),
             "ekf_sim_eval_match": (_i, [_vp, _d, _vp, _vp, _vp]),
+            "ekf_sim_lidar_config_default": (None, [C.POINTER(LidarConfig)]),
+            "ekf_sim_run_lidar": (_i, [_vp, _vp, _i, _vp, C.POINTER(LidarConfig)]),
+            "lm_fetch_ranges": (_i, [_vp, _vp]),
         }
         for name, (res, argt) in sig.items():
             # (EKF_LIB naming a library built from an earlier commit, for the A/B tools: it loads
@@ -708,6 +719,22 @@ class Sim:
         _check(lib().ekf_sim_run_assoc(self.h, T, _ptr(cmd)), "ekf_sim_run_assoc")
         self.T = T
 
+    def run_lidar(self, det, wheel_cmd, **cfg):
+        """ekf_sim_run_lidar: the same simulation, then the real sensor path on the device — the
+        laser scans every (message, filter) from its true pose on the front-end handle ``det``
+        (pyekf.landmarks.Detector), which detects on them, and the filter takes the detected markers
+        with unknown association. wheel_cmd[T·ticks][2]. ``cfg``: ekf_sim_lidar_config fields
+        (n_beams, max_markers, threshold, obstacle_radius), lm_scan_config fields for its ``scan``
+        (seed, arena_w, arena_h, range_min, range_max, sigma) or ``arena=(w, h)``."""
+        cmd = _f64(wheel_cmd).reshape(-1, 2)
+        T = cmd.shape[0] // self.cfg.ticks_per_msg
+        c = lidar_config(**cfg)
+        _check(lib().ekf_sim_run_lidar(self.h, det.h, T, _ptr(cmd), C.byref(c)),
+               "ekf_sim_run_lidar")
+        self.T = T
+        if T > 0:
+            det._ran_lidar(T * self.F, c.n_beams, c.max_markers)
+
     def markers(self):
         """The last run's inputs as ekf_replay takes them: counts [T,F], ids/actions [T,F,M],
         rel [T,F,M,2]."""
@@ -754,6 +781,24 @@ class Sim:
             self.close()
         except Exception:
             pass
+
+
+def lidar_config(**cfg) -> LidarConfig:
+    """ekf_sim_lidar_config_default with fields set: its own, its ``scan``'s (lm_scan_config), or
+    ``arena=(w, h)``."""
+    c = LidarConfig()
+    lib().ekf_sim_lidar_config_default(C.byref(c))
+    if "arena" in cfg:
+        c.scan.arena_w, c.scan.arena_h = cfg.pop("arena")
+    own, scan = dict(LidarConfig._fields_), dict(ScanConfig._fields_)
+    for name, v in cfg.items():
+        if name in own and name != "scan":
+            setattr(c, name, v)
+        elif name in scan:
+            setattr(c.scan, name, v)
+        else:
+            raise TypeError(f"unknown lidar setting {name!r}")
+    return c
 
 
 def eval_summary(recs) -> dict:

@@ -33,6 +33,7 @@ class Detector:
     def __init__(self, max_scans=1, max_beams=360, device=0):
         self.h = C.c_void_p()
         self._resident = 0  # scans the last simulate() left on the device
+        self._capacity = (max_scans, max_beams)
         _check(lib().lm_create(C.byref(self.h), max_scans, max_beams, device), "lm_create")
 
     def close(self):
@@ -111,7 +112,22 @@ class Detector:
                                  None if sc is None else sc.ctypes.data, C.byref(k),
                                  None if out is None else out.ctypes.data), "lm_simulate")
         self._resident = S
+        self._beams = n_beams
         return out
+
+    def _ran_lidar(self, S, n_beams, max_markers):
+        """Sim.run_lidar left S scans and their detect_device results in this handle."""
+        self._resident, self._beams = S, n_beams
+        self._device = (S, max_markers)
+
+    def fetch_ranges(self):
+        """lm_fetch_ranges: the resident scans (the last ``simulate``'s or ``Sim.run_lidar``'s) as
+        float32 [S, n_beams] (synchronising)."""
+        # (room for whatever the handle can hold: raw calls may have changed what is resident)
+        buf = np.zeros(self._capacity[0] * self._capacity[1], dtype=np.float32)
+        _check(lib().lm_fetch_ranges(self.h, buf.ctypes.data), "lm_fetch_ranges")
+        S, B = self._resident, getattr(self, "_beams", 0)
+        return buf[:S * B].reshape(S, B).copy()
 
     def detect_resident(self, threshold=0.2, max_markers=32):
         """``detect`` on the scans the last ``simulate`` left on the device (lm_detect_resident)."""

@@ -29,6 +29,8 @@
  * same markers and hands them to the filter with the ids ignored, and ekf_sim_eval_match matches the
  * slots the filter opened to the simulator's map on the device, scores them and reports the
  * association's quality (duplicate, spurious and missed landmarks).
+ * ekf_sim_run_lidar runs the real sensor path instead of the fake sensor: nusim's laser on the truth
+ * poses, the `landmarks` node's circle detection (landmarks.h), then the same association replay.
  *
  * Collisions with obstacles (nusim.cpp:232-254) are not modelled: landmarks are placed clear of
  * the path. */
@@ -36,6 +38,7 @@
 #define EKF_SIM_H
 
 #include "ekf.h"
+#include "landmarks.h" /* lm_t, lm_scan_config (ekf_sim_run_lidar) */
 
 #ifdef __cplusplus
 extern "C" {
@@ -98,6 +101,43 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense);
  * marker_stride > 64 (the replays' m_max limit), a pipeline handle on the one-marker route
  * (ekf_get_assoc_route: EKF_ASSOC_MARKER). T == 0: EKF_OK. */
 int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd);
+
+/* T messages through the real sensor path (unknown_data_assoc.launch.py: laser, circle detection,
+ * Mahalanobis association), none of it leaving the device. The wheels and the truth poses are
+ * simulated exactly as by ekf_sim_run_assoc (the fake sensor's markers are still written, so the
+ * record and ekf_sim_markers hold, and the call may alternate with ekf_sim_run and
+ * ekf_sim_run_assoc on one simulator: all three advance the same tick and message counters). Then,
+ * on the front-end handle `lm`: nusim's laser (lm_simulate, landmarks.h) scans every (message,
+ * filter) from its true pose against the filter's own map, each landmark a cylinder of
+ * obstacle_radius, into the handle's range buffer — scan t*F + f is message t of filter f — and
+ * the handle detects on them (lm_detect_device: n_beams, threshold, max_markers); the detected
+ * markers go to the filter as lm_replay_into / lm_replay_resident would feed them, with the
+ * simulator's own odometry. The laser's noise is sharded as the simulator's: scan (t, f) draws
+ * under scan.seed + f0 + f, beam b taking normal draw (msg0 + t)*n_beams + b of stream 6, msg0 the
+ * simulator's message counter before the run — the bits of lm_simulate called per filter with that
+ * seed and scan0 = msg0, so a run split into several calls, or a swarm split over ranks by f0,
+ * gives the bits of the single call.
+ * Afterwards `lm` holds the scans and the markers as after lm_simulate + lm_detect_device
+ * (lm_fetch_ranges, lm_fetch_markers, lm_last_simulate_us); the filter handle is as after those
+ * replays. Nothing crosses PCIe but the wheel commands; asynchronous (the host waits for nothing).
+ * Collisions are still not modelled: the caller keeps the drive clear of the cylinders, and a lidar
+ * inside a cylinder is outside the laser's documented domain (lidar_kernels.hip).
+ * EKF_E_ARG, and nothing changes and no counter advances: a NULL simulator, lm or cfg; T < 0, NULL
+ * wheel_cmd with T > 0; T*F > lm's max_scans; n_beams outside [2, lm's max_beams]; max_markers
+ * outside [1, 64]; obstacle_radius negative or NaN; an invalid scan (lm_simulate's rules:
+ * sigma < 0 or NaN, range_min > range_max); the two handles on different devices; a pipeline
+ * filter handle on the one-marker route (ekf_get_assoc_route: EKF_ASSOC_MARKER). T == 0: EKF_OK. */
+typedef struct {
+  int n_beams;             /* 360 */
+  int max_markers;         /* detections kept per scan, 1..64; 32 */
+  double threshold;        /* cluster break, 0.2 */
+  double obstacle_radius;  /* every landmark's cylinder radius, 0.038 */
+  lm_scan_config scan;     /* seed, arena, range_min/max, sigma; scan0 is ignored (the simulator's
+                              message counter takes its place) */
+} ekf_sim_lidar_config;
+void ekf_sim_lidar_config_default(ekf_sim_lidar_config*);
+int ekf_sim_run_lidar(ekf_sim_t s, lm_t lm, int T, const double* wheel_cmd,
+                      const ekf_sim_lidar_config* cfg);
 
 /* With cfg.record: the last run's inputs as ekf_replay would take them — counts[T][F],
  * ids/actions[T][F][M], rel_xy[T][F][M][2] (M = marker_stride) — and odom[T][3] (t_odom_robot) and

@@ -95,8 +95,13 @@ int lm_simulate(lm_t h, int n_scans, int n_beams, const double* poses, int n_sce
 /* lm_detect on the resident scans of the last lm_simulate: no range upload. EKF_E_ARG when
  * nothing is resident (no lm_simulate yet, or an lm_detect since overwrote the range buffer). */
 int lm_detect_resident(lm_t h, double threshold, lm_marker* markers, int max_markers, int* counts);
-/* Device time of the last lm_simulate's kernel (HIP events around the dispatch), microseconds. */
+/* Device time of the last scan kernel, lm_simulate's or ekf_sim_run_lidar's (ekf_sim.h), from HIP
+ * events around the dispatch, microseconds. */
 int lm_last_simulate_us(lm_t h, double* us);
+/* The resident scans (the last lm_simulate's or ekf_sim_run_lidar's) to the host: out
+ * [n_scans][n_beams] float, synchronising; for tests and inspection. EKF_E_ARG when nothing is
+ * resident. */
+int lm_fetch_ranges(lm_t h, float* out);
 
 /* ---- scans to posterior without a host hop ---- */
 
