@@ -10,6 +10,10 @@
 // to the device-input association replay of the handle's path.
 // ekf_sim_run_lidar simulates likewise, then has a landmark front-end handle scan the truth poses
 // with the laser kernel and detect on the scans (lm_api.cpp's hook), and replays those markers.
+// Collisions (ekf_sim_set_collisions) swap the wheel walk's kernel of either form for its collision
+// variant and nothing else; the per-message counts go into a buffer pair of their own, allocated by
+// the first run with collisions on, so a simulator that never turns them on allocates, launches and
+// frees exactly what it did before.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,6 +79,17 @@ struct ekf_sim {
   int last_T = 0, last_b = 0;
   std::vector<int> host_par;
   std::vector<double> host_odom;    // [F][3] t_odom_robot after the last run
+  // collisions (ekf_sim_set_collisions): R = collision_radius + obstacle_radius, 0: off
+  double hit_r = 0.0;
+  DeviceBuf<int> hits[2];           // [T][F] colliding ticks per message, by marker buffer
+  bool last_hits = false;           // the last run wrote hits[last_b]
+  // maps of fewer landmarks are staged whole (kCollideCullFromMap; EKF_SIM_CULL_FROM at
+  // ekf_sim_create overrides it for tools/sim_collide_bench.py and the tests: same bits)
+  int cull_from = kCollideCullFromMap;
+  // EKF_SIM_TIMING=1 at ekf_sim_create: timing events around each run's simulator launches
+  // (ekf_sim_last_us; tools/sim_collide_bench.py). Unset, nothing is created or recorded.
+  bool timing = false, timed = false;
+  Event ev_t0, ev_t1;
 };
 
 namespace {
@@ -142,6 +157,33 @@ int reserve(ekf_sim* s, int T) {
   return EKF_OK;
 }
 
+// The per-message collision counts of a run of T messages (with collisions on and a record kept
+// only; grown, never shrunk). The kernels that wrote the old blocks are waited for before a
+// regrowth frees them.
+int reserve_hits(ekf_sim* s, int T) {
+  if (!(s->hit_r > 0.0) || !s->cfg.record) return EKF_OK;
+  const size_t n = static_cast<size_t>(T) * s->info.F;
+  if (n <= s->hits[0].capacity() && n <= s->hits[1].capacity()) return EKF_OK;
+  if (hipStreamSynchronize(s->sst.get()) != hipSuccess) return EKF_E_HIP;
+  if (s->hits[0].reserve(n) || s->hits[1].reserve(n)) return reset_all(s->hits[0], s->hits[1]);
+  return EKF_OK;
+}
+
+// the collision settings of a launch; `record`: the per-message counts are kept (buffer b)
+bool set_collide(ekf_sim* s, SimArgs& a, bool record, int b) {
+  const bool on = s->hit_r > 0.0;
+  a.hit_r = s->hit_r;
+  a.out_hits = on && record ? s->hits[b].get() : nullptr;
+  a.cull_from = s->cull_from;
+  s->last_hits = on && record;
+  return on;
+}
+
+// the timing events around a run's simulator launches (EKF_SIM_TIMING)
+bool stamp(ekf_sim* s, Event& e) {
+  return !s->timing || hipEventRecord(e.get(), s->sst.get()) == hipSuccess;
+}
+
 // The simulation of the parallel form into run buffer b, on the simulator's stream; the handle's
 // streams wait for it. Advances the tick and message counters.
 int simulate_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sense, int b) {
@@ -182,7 +224,10 @@ int simulate_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sen
   a.range = s->cfg.max_range;
   a.radius = s->cfg.wheel_radius;
   a.track = s->cfg.track_width;
-  if (launch_sim_parallel(a, k.truth.get(), k.odomF.get(), st) != hipSuccess ||
+  const bool collide = set_collide(s, a, s->cfg.record != 0, b);
+  if (!stamp(s, s->ev_t0) ||
+      launch_sim_parallel(a, collide, k.truth.get(), k.odomF.get(), st) != hipSuccess ||
+      !stamp(s, s->ev_t1) ||
       hipEventRecord(s->ev_sim.get(), st) != hipSuccess ||
       hipStreamWaitEvent(s->info.stream, s->ev_sim.get(), 0) != hipSuccess ||
       hipStreamWaitEvent(s->info.bulk, s->ev_sim.get(), 0) != hipSuccess)
@@ -191,6 +236,7 @@ int simulate_parallel(ekf_sim* s, int T, const double* wheel_cmd, const int* sen
   s->msg += T;
   s->last_T = T;
   s->last_b = b;
+  s->timed = s->timing;
   return EKF_OK;
 }
 
@@ -338,6 +384,16 @@ int ekf_sim_create(ekf_sim_t* out, ekf_t filter, const ekf_sim_config* cfg, int 
       hipMemset(s->sighted.get(), 0, F * words * sizeof(unsigned)) != hipSuccess ||
       hipMemcpy(s->st.get(), st.data(), F * sizeof(SimState), hipMemcpyHostToDevice) != hipSuccess)
     return fail(EKF_E_HIP);
+  if (const char* from = std::getenv("EKF_SIM_CULL_FROM")) {  // (digits only: anything else is
+    char* end = nullptr;                                        // ignored, not read as 0)
+    const long v = std::strtol(from, &end, 10);
+    if (end != from && *end == '\0' && v >= 0) s->cull_from = static_cast<int>(std::min(v, 1L << 20));
+  }
+  const char* tm = std::getenv("EKF_SIM_TIMING");
+  if (tm && std::atoi(tm) != 0) {
+    if (s->ev_t0.create() || s->ev_t1.create()) return fail(EKF_E_HIP);
+    s->timing = true;
+  }
   s->host_par.assign(F, 0);
   s->host_odom.assign(3 * F, 0.0);
   *out = s;
@@ -367,6 +423,7 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense) {
   const bool par = parallel_ok(s, T, sense);
   hipSetDevice(s->info.device);
   if (int rc = reserve(s, T)) return rc;
+  if (int rc = reserve_hits(s, T)) return rc;
   if (par) return run_parallel(s, T, wheel_cmd, sense);
   const int b = s->buf;
   s->buf ^= 1;
@@ -423,7 +480,12 @@ int ekf_sim_run(ekf_sim_t s, int T, const double* wheel_cmd, const int* sense) {
   a.radius = s->cfg.wheel_radius;
   a.track = s->cfg.track_width;
   a.joseph = s->info.joseph && !s->info.resident;
-  if (launch_sim(a, st) != hipSuccess) return EKF_E_HIP;
+  // (the record, the counts included, is marker buffer 0's)
+  if (!stamp(s, s->ev_t0) ||
+      launch_sim(a, set_collide(s, a, s->cfg.record != 0, 0), st) != hipSuccess ||
+      !stamp(s, s->ev_t1))
+    return EKF_E_HIP;
+  s->timed = s->timing;
   // each filter's final parity (its inactive messages do not flip it) and odometry: the host mirror
   if (hipMemcpyAsync(s->host_par_pinned.get(), s->par.get(), F * sizeof(int),
                      hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -460,6 +522,7 @@ int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd) {
   hipSetDevice(s->info.device);
   s->assoc = true;
   if (int rc = reserve(s, T)) return rc;
+  if (int rc = reserve_hits(s, T)) return rc;
   return run_assoc(s, T, wheel_cmd);
 }
 
@@ -492,7 +555,45 @@ int ekf_sim_run_lidar(ekf_sim_t s, lm_t lm, int T, const double* wheel_cmd,
   hipSetDevice(s->info.device);
   s->assoc = true;  // both marker buffers: the replay reads this run's odometry from its own
   if (int rc = reserve(s, T)) return rc;
+  if (int rc = reserve_hits(s, T)) return rc;
   return run_lidar(s, lm, T, wheel_cmd, cfg);
+}
+
+int ekf_sim_set_collisions(ekf_sim_t s, double collision_radius, double obstacle_radius) {
+  if (!s || !(collision_radius >= 0.0) || !(obstacle_radius >= 0.0)) return EKF_E_ARG;
+  s->hit_r = collision_radius > 0.0 ? collision_radius + obstacle_radius : 0.0;
+  return EKF_OK;
+}
+
+int ekf_sim_collisions(ekf_sim_t s, long long* total, int* per_msg) {
+  if (!s || !total || (per_msg && !s->cfg.record)) return EKF_E_ARG;
+  const size_t F = static_cast<size_t>(s->info.F), n = static_cast<size_t>(s->last_T) * F;
+  hipSetDevice(s->info.device);
+  if (hipStreamSynchronize(s->info.stream) != hipSuccess ||
+      hipStreamSynchronize(s->sst.get()) != hipSuccess)
+    return EKF_E_HIP;
+  std::vector<SimState> st(F);
+  if (hipMemcpy(st.data(), s->st.get(), F * sizeof(SimState), hipMemcpyDeviceToHost) != hipSuccess)
+    return EKF_E_HIP;
+  for (size_t f = 0; f < F; ++f) total[f] = st[f].hits;
+  if (per_msg && n) {
+    if (!s->last_hits)  // the last run had collisions off
+      std::memset(per_msg, 0, n * sizeof(int));
+    else if (hipMemcpy(per_msg, s->hits[s->last_b].get(), n * sizeof(int),
+                       hipMemcpyDeviceToHost) != hipSuccess)
+      return EKF_E_HIP;
+  }
+  return EKF_OK;
+}
+
+int ekf_sim_last_us(ekf_sim_t s, double* us) {
+  if (!s || !us || !s->timed) return EKF_E_ARG;
+  float ms = 0.0f;
+  if (hipEventSynchronize(s->ev_t1.get()) != hipSuccess ||
+      hipEventElapsedTime(&ms, s->ev_t0.get(), s->ev_t1.get()) != hipSuccess)
+    return EKF_E_HIP;
+  *us = 1e3 * static_cast<double>(ms);
+  return EKF_OK;
 }
 
 int ekf_sim_markers(ekf_sim_t s, int* counts, int* ids, int* actions, double* rel_xy) {

@@ -52,6 +52,7 @@ EXPORTS = [
     "ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval",
     "ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match",
     "ekf_sim_lidar_config_default", "ekf_sim_run_lidar", "lm_fetch_ranges",
+    "ekf_sim_set_collisions", "ekf_sim_collisions", "ekf_sim_last_us",
 ]
 TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear",
                  "slam_replay_trace")
@@ -59,8 +60,11 @@ TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_t
 EVAL_EXPORTS = ("ekf_get_marginals", "ekf_eval", "ekf_eval_summary", "ekf_sim_eval")
 MATCH_EXPORTS = ("ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match")
 LIDAR_EXPORTS = ("ekf_sim_lidar_config_default", "ekf_sim_run_lidar", "lm_fetch_ranges")
+COLLIDE_EXPORTS = ("ekf_sim_set_collisions", "ekf_sim_collisions")
+SIM_DEV_EXPORTS = ("ekf_sim_last_us",)  # measurement hook (EKF_SIM_TIMING), not part of the feature
 LATER_EXPORTS = (TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident") + EVAL_EXPORTS +
-                 MATCH_EXPORTS + ("ekf_chain_path_counts",) + LIDAR_EXPORTS)
+                 MATCH_EXPORTS + ("ekf_chain_path_counts",) + LIDAR_EXPORTS + COLLIDE_EXPORTS +
+                 SIM_DEV_EXPORTS)
 EKF_MATCH_MAX_MAP = 1024
 EKF_EVAL_POSE_NOT_PD, EKF_EVAL_LM_NOT_PD = 1, 2
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
@@ -251,6 +255,9 @@ def lib():
             "ekf_sim_lidar_config_default": (None, [C.POINTER(LidarConfig)]),
             "ekf_sim_run_lidar": (_i, [_vp, _vp, _i, _vp, C.POINTER(LidarConfig)]),
             "lm_fetch_ranges": (_i, [_vp, _vp]),
+            "ekf_sim_set_collisions": (_i, [_vp, _d, _d]),
+            "ekf_sim_collisions": (_i, [_vp, _vp, _vp]),
+            "ekf_sim_last_us": (_i, [_vp, _dp]),
         }
         for name, (res, argt) in sig.items():
             # (EKF_LIB naming a library built from an earlier commit, for the A/B tools: it loads
@@ -734,6 +741,27 @@ class Sim:
         self.T = T
         if T > 0:
             det._ran_lidar(T * self.F, c.n_beams, c.max_markers)
+
+    def set_collisions(self, collision_radius, obstacle_radius=0.038):
+        """ekf_sim_set_collisions: from the next run on the true pose is pushed out of the map's
+        cylinders (nusim.cpp:232-254), R = collision_radius + obstacle_radius; 0 turns it off."""
+        _check(lib().ekf_sim_set_collisions(self.h, float(collision_radius),
+                                            float(obstacle_radius)), "ekf_sim_set_collisions")
+
+    def collisions(self, per_msg=True):
+        """ekf_sim_collisions: (total [F] colliding ticks per filter since the simulator was made,
+        per_msg [T, F] of the last run; None without ``per_msg``, which needs cfg.record)."""
+        total = np.zeros(self.F, np.int64)
+        pm = np.zeros((self.T, self.F), np.int32) if per_msg else None
+        _check(lib().ekf_sim_collisions(self.h, _ptr(total), _ptr(pm)), "ekf_sim_collisions")
+        return total, pm
+
+    def last_us(self):
+        """ekf_sim_last_us: µs between the HIP events around the last run's simulator launches (a
+        simulator made with EKF_SIM_TIMING=1 in the environment)."""
+        us = C.c_double(0.0)
+        _check(lib().ekf_sim_last_us(self.h, C.byref(us)), "ekf_sim_last_us")
+        return us.value
 
     def markers(self):
         """The last run's inputs as ekf_replay takes them: counts [T,F], ids/actions [T,F,M],

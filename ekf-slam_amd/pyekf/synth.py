@@ -183,9 +183,40 @@ def _fkin_step(config, dl, dr, radius=WHEEL_RADIUS, track=TRACK_WIDTH):
     return _compose(config, d)
 
 
-def _simulate(drive: Drive, seeds: np.ndarray, start_pose, slip: float):
+def _collide(config, landmarks, R):
+    """nusim's obstacle loop (nusim.cpp:232-254) on the poses ``config`` of F filters, after a
+    tick's FKin: each filter's landmarks [F, L, 2] are tested in id order, and the pose is pushed
+    out of the first one it is inside (d < R) along the line of centres, θ kept; no further landmark
+    is tested for that filter in this tick. → (config, hit [F] bool, the smallest |d − R| over the
+    tests that ran: those up to and including the colliding id)."""
+    th, x, y = config
+    dx = x[:, None] - landmarks[..., 0]
+    dy = y[:, None] - landmarks[..., 1]
+    d = np.sqrt(dx * dx + dy * dy)                                      # [F, L]
+    inside = d < R
+    hit = inside.any(1)
+    first = np.where(hit, inside.argmax(1), landmarks.shape[1] - 1)     # the last test that ran
+    ran = np.arange(landmarks.shape[1])[None, :] <= first[:, None]
+    edge = float(np.abs(d - R)[ran].min())
+    rows = np.arange(x.shape[0])
+    lx, ly, dd = landmarks[rows, first, 0], landmarks[rows, first, 1], d[rows, first]
+    a = np.arctan2(ly - y, lx - x)
+    x = np.where(hit, x - (R - dd) * np.cos(a), x)
+    y = np.where(hit, y - (R - dd) * np.sin(a), y)
+    return (th, x, y), hit, edge
+
+
+def _simulate(drive: Drive, seeds: np.ndarray, start_pose, slip: float, landmarks=None,
+              collision_radius: float = 0.0, obstacle_radius: float = 0.0):
     """True poses of F filters → (wheel [T, ticks, 2] encoder angles shared by all filters,
     truth [F, T, 3] at the messages, path [F, ticks_total, 2] positions).
+
+    With ``landmarks`` [F, L, 2] (or [L, 2]: every filter's) and ``collision_radius`` > 0 the true
+    pose collides with the landmarks' cylinders of ``obstacle_radius`` (``_collide``, once per tick
+    after FKin, R = collision_radius + obstacle_radius; the wheel angles are not reset, so the next
+    tick's arc composes onto the corrected pose, and the encoders go on as commanded), and two more
+    values are returned: hits [F, T] colliding ticks per message and the smallest |d − R| over every
+    test that ran (how far the run is from a different decision). Without them nothing changes.
 
     nusim's timer (nusim.cpp:222-230): each tick a wheel turns by its commanded increment ×
     (1 + U(−slip, slip)), and the true pose is DiffDrive::FKin of the accumulated true wheel angles
@@ -211,16 +242,28 @@ def _simulate(drive: Drive, seeds: np.ndarray, start_pose, slip: float):
     phi_r = np.zeros(F)
     path = np.zeros((F, nt, 2))
     truth = np.zeros((F, T, 3))
+    collide = landmarks is not None and collision_radius > 0.0
+    if collide:
+        lm = np.broadcast_to(np.asarray(landmarks, np.float64), (F,) + np.shape(landmarks)[-2:])
+        R = collision_radius + obstacle_radius
+        hits = np.zeros((F, T), np.int32)
+        edge = math.inf
     for i in range(nt):
         nl = phi_l + slipped[:, i, 0]
         nr = phi_r + slipped[:, i, 1]
         config = _fkin_step(config, nl - phi_l, nr - phi_r)
         phi_l, phi_r = nl, nr
+        if collide:
+            config, hit, e = _collide(config, lm, R)
+            hits[:, i // tpm] += hit
+            edge = min(edge, e)
         path[:, i, 0] = config[1]
         path[:, i, 1] = config[2]
         if (i + 1) % tpm == 0:
             t = (i + 1) // tpm - 1
             truth[:, t, 0], truth[:, t, 1], truth[:, t, 2] = config
+    if collide:
+        return wheel, truth, path, hits, edge
     return wheel, truth, path
 
 
@@ -358,6 +401,8 @@ class Swarm:
     cmd: np.ndarray = field(default=None, repr=False)      # [T·ticks, 2] commanded wheel increments
     sense: np.ndarray = field(default=None, repr=False)    # [T] SENSE_* per message
     start_pose: tuple = (0.0, 0.0, -1.0)                   # true (θ, x, y) at the first tick
+    hits: np.ndarray = field(default=None, repr=False)     # [T, F] colliding ticks (collisions on)
+    hit_edge: float = math.inf                             # the smallest |d − R| of their tests
 
     @property
     def n_filters(self) -> int:
@@ -376,12 +421,21 @@ class Swarm:
 
 def _generate(n_landmarks, drive: Drive, seeds, landmarks=None, half=None, *, max_markers=16,
               start_pose=(0.0, 0.0, -1.0), sensor_sigma=1e-3, slip=0.02, max_range=5.0,
-              shuffle=False, n_delete=0, clearance=0.3, n_map=None, marker_stride=None) -> Swarm:
+              shuffle=False, n_delete=0, clearance=0.3, n_map=None, marker_stride=None,
+              collision_radius=0.0, obstacle_radius=0.0) -> Swarm:
+    """``collision_radius`` > 0 (with ``landmarks`` given: a map placed clear of the path has
+    nothing to hit): the true poses collide with the landmarks' cylinders (``_simulate``)."""
     seeds = np.asarray(seeds, dtype=np.uint64).reshape(-1)
     F = seeds.shape[0]
     if drive.start_pose is not None:
         start_pose = drive.start_pose
-    wheel, truth, path = _simulate(drive, seeds, start_pose, slip)
+    hits, edge = None, math.inf
+    if landmarks is not None and collision_radius > 0.0:
+        wheel, truth, path, hits, edge = _simulate(drive, seeds, start_pose, slip, landmarks,
+                                                   collision_radius, obstacle_radius)
+        hits = np.ascontiguousarray(hits.T)
+    else:
+        wheel, truth, path = _simulate(drive, seeds, start_pose, slip)
     tpm = drive.ticks_per_msg
     dt = 1.0 / drive.tick_hz
     cmd = np.stack([(drive.v - drive.w * TRACK_WIDTH / 2.0) / WHEEL_RADIUS * dt,
@@ -399,7 +453,7 @@ def _generate(n_landmarks, drive: Drive, seeds, landmarks=None, half=None, *, ma
                                          marker_stride)
     return Swarm(n_landmarks, seeds, landmarks, wheel, ids, act, rel, cnt,
                  np.ascontiguousarray(truth.transpose(1, 0, 2)), drive.n_warm, sighted, cmd,
-                 drive.sense.copy(), tuple(float(v) for v in start_pose))
+                 drive.sense.copy(), tuple(float(v) for v in start_pose), hits, edge)
 
 
 def make_scenario(n_landmarks: int, landmarks: np.ndarray, n_messages: int, *,

@@ -32,8 +32,10 @@
  * ekf_sim_run_lidar runs the real sensor path instead of the fake sensor: nusim's laser on the truth
  * poses, the `landmarks` node's circle detection (landmarks.h), then the same association replay.
  *
- * Collisions with obstacles (nusim.cpp:232-254) are not modelled: landmarks are placed clear of
- * the path. */
+ * Collisions with obstacles (nusim.cpp:232-254) are off by default and turned on by
+ * ekf_sim_set_collisions: after each tick's FKin the true pose is tested against the map's cylinders
+ * in id order and pushed out of the first one it is inside, while the wheels and the odometry go
+ * on as commanded. */
 #ifndef EKF_SIM_H
 #define EKF_SIM_H
 
@@ -120,8 +122,10 @@ int ekf_sim_run_assoc(ekf_sim_t s, int T, const double* wheel_cmd);
  * Afterwards `lm` holds the scans and the markers as after lm_simulate + lm_detect_device
  * (lm_fetch_ranges, lm_fetch_markers, lm_last_simulate_us); the filter handle is as after those
  * replays. Nothing crosses PCIe but the wheel commands; asynchronous (the host waits for nothing).
- * Collisions are still not modelled: the caller keeps the drive clear of the cylinders, and a lidar
- * inside a cylinder is outside the laser's documented domain (lidar_kernels.hip).
+ * With collisions on (ekf_sim_set_collisions with the same obstacle_radius and a collision_radius
+ * of at least the lidar's 0.032 m mount offset; cylinders that do not overlap) the truth poses
+ * keep the lidar out of every cylinder; with them off the caller keeps the drive clear of the
+ * cylinders, as a lidar inside one is outside the laser's documented domain (lidar_kernels.hip).
  * EKF_E_ARG, and nothing changes and no counter advances: a NULL simulator, lm or cfg; T < 0, NULL
  * wheel_cmd with T > 0; T*F > lm's max_scans; n_beams outside [2, lm's max_beams]; max_markers
  * outside [1, 64]; obstacle_radius negative or NaN; an invalid scan (lm_simulate's rules:
@@ -138,6 +142,34 @@ typedef struct {
 void ekf_sim_lidar_config_default(ekf_sim_lidar_config*);
 int ekf_sim_run_lidar(ekf_sim_t s, lm_t lm, int T, const double* wheel_cmd,
                       const ekf_sim_lidar_config* cfg);
+
+/* Collisions with the map's cylinders (nusim.cpp:232-254), for ekf_sim_run, ekf_sim_run_assoc and
+ * ekf_sim_run_lidar alike. Once per tick, after FKin, with the true pose at (x, y, θ) the landmarks
+ * are tested in id order, R = collision_radius + obstacle_radius:
+ *   d = sqrt((x − lx)·(x − lx) + (y − ly)·(y − ly));  if d < R:  a = atan2(ly − y, lx − x),
+ *   x ← x − (R − d)·cos a,  y ← y − (R − d)·sin a,  θ kept, and no further landmark is tested in
+ *   this tick (only the lowest colliding id acts).
+ * The next tick's arc composes onto the corrected pose; the odometry is untouched (the encoders
+ * report the commanded angles), so it runs away from the truth while the robot is held. At d = 0
+ * the push goes along −x (atan2(0, 0) = 0). nusim's TF broadcast inside that loop is not mirrored.
+ * collision_radius > 0 turns collisions on from the next run; 0 turns them off (the default: the
+ * simulator then launches the same kernels and gives the same bits as without this call, and so
+ * does a run with collisions on in which nothing is hit). obstacle_radius >= 0 is every landmark's
+ * cylinder radius. EKF_E_ARG, nothing changes: NULL simulator, a negative or NaN radius. */
+int ekf_sim_set_collisions(ekf_sim_t s, double collision_radius, double obstacle_radius);
+
+/* total[F]: colliding ticks per filter since ekf_sim_create. per_msg[T][F] (nullable; needs
+ * cfg.record): colliding ticks in each message of the last run. Synchronises. EKF_E_ARG: a NULL
+ * simulator or total, per_msg without cfg.record. */
+int ekf_sim_collisions(ekf_sim_t s, long long* total, int* per_msg);
+
+/* A development hook, not part of the simulation's interface: measurement
+ * (tools/sim_collide_bench.py), as lm_last_simulate_us is for the laser. A simulator created with EKF_SIM_TIMING=1 in the
+ * environment records HIP events around each run's simulator launches (the wheel walk and the
+ * sensing, on the simulator's stream; not the filter's work); us gets the last run's time between
+ * them, in µs. Waits for that run's simulation. EKF_E_ARG: a NULL simulator or us, a simulator
+ * created without EKF_SIM_TIMING, no run yet. */
+int ekf_sim_last_us(ekf_sim_t s, double* us);
 
 /* With cfg.record: the last run's inputs as ekf_replay would take them — counts[T][F],
  * ids/actions[T][F][M], rel_xy[T][F][M][2] (M = marker_stride) — and odom[T][3] (t_odom_robot) and
