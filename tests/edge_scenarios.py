@@ -282,22 +282,24 @@ def last_slot_scenario(N: int):
                           sc.count, sc.truth, sc.track, sc.radius, sc.n_warm)
 
 
-def forget_last(x, S):
-    """The last landmark slot back to the prior (slam.cpp:127-132), in place."""
+def forget_last(x, S, init_var=10e6):
+    """The last landmark slot back to the prior (slam.cpp:127-132; `init_var`: the filter's, by
+    default the reference's), in place."""
     k = x.shape[0] - 2
     x[k:] = 0.0
     S[k:, :] = 0.0
     S[:, k:] = 0.0
-    S[k, k] = S[k + 1, k + 1] = 10e6
+    S[k, k] = S[k + 1, k + 1] = init_var
 
 
 # ---- the oracle -----------------------------------------------------------------------------------
-def run_oracle(e: Edge, literal=False, joseph=False):
-    """The oracle through every message of `e` → rcs [T], poses [T, 3], final state / sigma / tmo /
+def run_oracle(e: Edge, literal=False, joseph=False, **params):
+    """The oracle (`params`: q_noise, r_noise, init_var, mah_gate where they are not the defaults)
+    through every message of `e` → rcs [T], poses [T, 3], final state / sigma / tmo /
     counter, the heading of t_map_odom * t_odom_robot before slam.cpp:186 normalises it (raw_theta
     [T]) and, under association, decisions j / new [T, M] and each marker's smallest existing
     Mahalanobis distance dmin [T, M] (NaN padded)."""
-    ref = orc.OracleEKF(n_landmarks=e.n_landmarks, literal=literal, joseph=joseph)
+    ref = orc.OracleEKF(n_landmarks=e.n_landmarks, literal=literal, joseph=joseph, **params)
     T, M = e.ids.shape
     rcs = np.zeros(T, np.int32)
     poses = np.zeros((T, 3))
