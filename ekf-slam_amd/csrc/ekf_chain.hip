@@ -26,8 +26,10 @@
 //   issue_early_loads         kLook, staged: the image and the previous record → ChainLoads
 //   build_index_sets          A0: U and U'
 //   rebuild_block             A1, kLook: land_rebuild_operands (staged image, or its own gather and
-//                             store_raw_image), predict_prev, rebuild_km_simple / _joseph (K', M';
-//                             wave 3: x_in[U]), rebuild_p_simple / _joseph, pick_predicted_pose
+//                             store_raw_image), predict_prev (wave 3: map_U_into_prev),
+//                             rebuild_km_simple / _joseph (K', M'; simple form, wave 3: x_in[U]),
+//                             rebuild_p_simple / _joseph (Joseph form, wave 3: x_in[U]),
+//                             pick_predicted_pose
 //   gather_block              A1 otherwise: Σ_in[U, U], x[U] and the predicted pose from HBM
 //   fold_predict              A3: this chunk's predict on the block
 //   chain_wave0 (_lean) .. 3  A2: the corrections; Z (wave 1), Y (wave 2), the rest of the block,
@@ -104,6 +106,7 @@ struct ChainSharedT {
   // kLook: the previous chunk's record and the blocks rebuilt from it
   struct {
     int u[kMaxU];
+    int pos[kMaxU];  // where this chunk's u_a sits in U' (map_U_into_prev)
     int nu, m, first, joseph;
     double a1, a2, s00;
     double xU[kMaxU], Zx[kMaxU];
@@ -825,19 +828,43 @@ __device__ __forceinline__ void land_rebuild_operands(ChainSharedT<J>& sh, Chain
   if (tid < 3) sh.tmo[tid] = L.tq;
 }
 
-// Wave 3's share of the K' / M' phase, x_in[U] of lane ln's row: the previous chunk's x[U'] where
-// it has it, else x' + r'(i)·Zx'.
+// Where each column of U sits in U' (pv.pos[a]: the first position k with u'_k = u_a; −1: none),
+// for x_in[U]. One wave (wave 3, beside the other waves' previous predict: off every barrier's
+// path), from the index sets: a landmark column is 3 + 2·slot + (x: 0, y: 1), so lane j < m' takes
+// the previous marker j's slot, and a lane's own slot is compared with the 16 of them by
+// v_readlane — the columns' comparison (a bad id's columns are slot 0's on both sides).
 template <bool J>
-__device__ __forceinline__ double prev_x_at_U(ChainSharedT<J>& sh, int ln, int np) {
-  const int l = ln < kMaxU ? ln : kMaxU - 1;
-  const int u = sh.u[l];
-  int pos = -1;
+__device__ __forceinline__ void map_U_into_prev(ChainSharedT<J>& sh, int ln, int nu) {
+  const int pm = sh.pv.m;
+  const int pslot = ln < pm ? (sh.pv.u[3 + 2 * min(ln, kMaxChunk - 1)] - 3) >> 1 : -1;
+  const int l = min(ln, kMaxU - 1), u = sh.u[l];
+  const int slot = (u - 3) >> 1, par = (u - 3) & 1;  // (a marker's; the pose is mapped below)
+  int hit = -1;
 #pragma unroll
-  for (int k = kMaxU - 1; k >= 0; --k) pos = (k < np && sh.pv.u[k] == u) ? k : pos;
+  for (int c = kMaxChunk - 1; c >= 0; --c)
+    hit = __builtin_amdgcn_readlane(pslot, c) == slot ? 3 + 2 * c + par : hit;
+  // the pose sits at its own position; a padding row's column 0 at position 0 (never stored)
+  if (ln < kMaxU) sh.pv.pos[ln] = l < 3 ? l : (l < nu ? hit : 0);
+}
+
+// Wave 3's x_in[U] of lane ln's row: the previous chunk's x[U'] where it has it (pv.pos), else
+// x' + r'(i)·Zx'. Nothing reads it before the predict fold. Simple form: beside wave 3's K' / M'
+// tiles, where it stands in for the band output the other waves have (one dot product each: wave 3
+// reaches the barrier before them). Joseph form: in the P phase, whose tiles are waves 0–2's.
+template <bool J>
+__device__ __forceinline__ double prev_x_at_U(ChainSharedT<J>& sh, int ln) {
+  const int l = ln < kMaxU ? ln : kMaxU - 1;
+  const int pos = sh.pv.pos[l];
   double bacc[4] = {0.0, 0.0, 0.0, 0.0};
   dot4<kMaxU>(&sh.im.R[l][0], &sh.pv.Zx[0], 1, bacc);
   const double r = sum4(bacc);  // R[·][k ≥ |U'|] = 0
   return pos >= 0 ? sh.pv.xU[pos] : sh.pv.xg[l] + r;
+}
+template <bool J>
+__device__ __forceinline__ void store_x_in(ChainSharedT<J>& sh, int ln, int nu, double xres) {
+  // (lanes beyond store to the wave's junk slot: a value used under a branch is computed there)
+  *(ln < nu ? &sh.xU[0][ln] : &sh.junk[3][ln]) = xres;
+  if (ln < 3) sh.xpose[ln] = sh.pv.xU[ln];  // pose ∈ U' always
 }
 
 // A band output of the K' / M' phase as a VALU dot product (16 × 16 tiles there would be 13/16
@@ -857,11 +884,14 @@ __device__ __forceinline__ void km_band_dot(ChainSharedT<J>& sh, bool bk, int br
 // unconditional (clamped rows / columns feed only discarded outputs, k ≥ |U'| is zero-padded in
 // both operands, so every k-step runs: its MFMA adds exact zeros). A wave's tiles and its VALU work
 // are one basic block (operand reads first, then two interleaved accumulation chains beside the dot
-// product): the MFMA and VALU pipes overlap.
+// product): the MFMA and VALU pipes overlap. The stores are unconditional too, through a selected
+// address: a store under a branch took the dot product into the branch with it, behind the MFMAs.
 template <bool W3>
 __device__ __forceinline__ void rebuild_km_simple(ChainSharedT<false>& sh, const ChainLane& L, int nu,
-                                                  int np) {
-  const int tid = L.tid, wv = L.wv, ln = L.ln, i16 = L.i16, k4 = L.k4;
+                                                  int np, unsigned seq) {
+  (void)seq;  // (diagnostic stamps)
+  (void)np;
+  const int tid = L.tid, wv = L.wv, i16 = L.i16, k4 = L.k4;
   double av[2][9], bv[2][9];
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
@@ -896,7 +926,7 @@ __device__ __forceinline__ void rebuild_km_simple(ChainSharedT<false>& sh, const
     }
     km_band_dot(sh, bk, brow, bcol, bacc);
   } else {
-    xres = prev_x_at_U(sh, ln, np);
+    xres = prev_x_at_U(sh, L.ln);
   }
   d4 acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
 #pragma unroll
@@ -910,30 +940,29 @@ __device__ __forceinline__ void rebuild_km_simple(ChainSharedT<false>& sh, const
     const int ti = (kt ? tt : tt - 4) >> 1, tj = (kt ? tt : tt - 4) & 1;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const double v = acc[q][r];
-      if (kt) sh.pv.K[16 * ti + k4 + 4 * r][16 * tj + i16] = v;
-      else sh.pv.M[16 * ti + k4 + 4 * r][16 * tj + i16] = v;
+      const int row = 16 * ti + k4 + 4 * r, col = 16 * tj + i16;
+      *(kt ? &sh.pv.K[row][col] : &sh.pv.M[row][col]) = acc[q][r];
     }
   }
-  if (!W3) {
-    const double v = sum4(bacc);
-    if (bk) sh.pv.K[brow][bcol] = v;
-    else if (bcol < kMaxU) sh.pv.M[brow][bcol] = v;
-  } else {
-    if (ln < nu) sh.xU[0][ln] = xres;
-    if (ln < 3) sh.xpose[ln] = sh.pv.xU[ln];  // pose ∈ U' always
-  }
+  EKF_STAMPW(30);  // (the wave's tiles stored)
+  if (!W3)  // (an M' band column is 32..34 < kMaxU)
+    *(bk ? &sh.pv.K[brow][bcol] : &sh.pv.M[brow][bcol]) = sum4(bacc);
+  else
+    store_x_in(sh, L.ln, nu, xres);
 }
 
 // Joseph form (ZC = 64): K' = R·Z' is 35 × 4m' (K' then V' columns), M' = Y'·C is 2m' × 35. Their
 // 16 × 16 cores are 12 tiles, three per wave (one after another, each operand read waited for
 // once); the bands K'[32..34][·] (192 outputs) and M'[·][32..34] (96) are VALU dot products of
-// waves 0–2 (two per thread for the first 96), wave 3 (W3) forms x_in[U] as in the simple form.
+// waves 0–2 (two per thread for the first 96); wave 3 (W3) has its tiles only.
 template <bool W3>
 __device__ __forceinline__ void rebuild_km_joseph(ChainSharedT<true>& sh, const ChainLane& L, int nu,
-                                                  int np) {
+                                                  int np, unsigned seq) {
+  (void)seq;  // (diagnostic stamps)
+  (void)nu;
+  (void)np;
   constexpr int ZC = ChainSharedT<true>::ZC;
-  const int tid = L.tid, wv = L.wv, ln = L.ln, i16 = L.i16, k4 = L.k4;
+  const int tid = L.tid, wv = L.wv, i16 = L.i16, k4 = L.k4;
 #pragma unroll 1
   for (int q = 0; q < 3; ++q) {
     const int tt = wv + 4 * q;  // 0..7 K' tiles (2 × 4), 8..11 M' tiles (2 × 2)
@@ -952,11 +981,12 @@ __device__ __forceinline__ void rebuild_km_joseph(ChainSharedT<true>& sh, const 
 #pragma unroll
     for (int s0 = 0; s0 < 9; ++s0) acc = mfma_f64(av[s0], bv[s0], acc);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (kt) sh.pv.K[16 * ti + k4 + 4 * r][16 * tj + i16] = acc[r];
-      else sh.pv.M[16 * ti + k4 + 4 * r][16 * tj + i16] = acc[r];
+    for (int r = 0; r < 4; ++r) {  // (a selected address, not a branch: rebuild_km_simple)
+      const int row = 16 * ti + k4 + 4 * r, col = 16 * tj + i16;
+      *(kt ? &sh.pv.K[row][col] : &sh.pv.M[row][col]) = acc[r];
     }
   }
+  EKF_STAMPW(30);  // (the wave's tiles stored)
   if (!W3) {
 #pragma unroll 1
     for (int t = tid; t < 288; t += 192) {
@@ -965,14 +995,12 @@ __device__ __forceinline__ void rebuild_km_joseph(ChainSharedT<true>& sh, const 
       const int brow = bk ? 32 + (t >> 6) : u / 3, bcol = bk ? (t & 63) : 32 + u % 3;
       double bacc[4] = {0.0, 0.0, 0.0, 0.0};
       km_band_dot(sh, bk, brow, bcol, bacc);
+      // (stored under a branch, unlike the tiles: without it this loop's reads were issued one
+      // by one, each waited for before its FMA)
       const double v = sum4(bacc);
       if (bk) sh.pv.K[brow][bcol] = v;
       else if (bcol < kMaxU) sh.pv.M[brow][bcol] = v;
     }
-  } else {
-    const double xres = prev_x_at_U(sh, ln, np);
-    if (ln < nu) sh.xU[0][ln] = xres;
-    if (ln < 3) sh.xpose[ln] = sh.pv.xU[ln];  // pose ∈ U' always
   }
 }
 
@@ -980,8 +1008,10 @@ __device__ __forceinline__ void rebuild_km_joseph(ChainSharedT<true>& sh, const 
 // M' rows ≥ 2m' are zero because Z' / Y' are, so every k-step runs: their MFMAs add exact zeros).
 // The 32 × 32 core of P on MFMA, one 16 × 16 tile per wave; the 3-wide bands (rows 32..34 and
 // columns 32..34, 201 entries) as VALU dot products, one per thread, in the same basic block.
+// Entries outside the block go to the wave's junk slot (a selected address: rebuild_km_simple).
 __device__ __forceinline__ void rebuild_p_simple(ChainSharedT<false>& sh, const ChainLane& L,
-                                                 int nu) {
+                                                 int nu, unsigned seq) {
+  (void)seq;  // (diagnostic stamps)
   auto& P = sh.im.D;
   const int tid = L.tid, wv = L.wv, i16 = L.i16, k4 = L.k4;
   const int ti = wv >> 1, tj = wv & 1;
@@ -1008,9 +1038,10 @@ __device__ __forceinline__ void rebuild_p_simple(ChainSharedT<false>& sh, const 
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = 16 * ti + k4 + 4 * r;
-    if (row < nu && col < nu) P[row][col] = acc[r];
+    *(row < nu && col < nu ? &P[row][col] : &sh.junk[wv][L.ln]) = acc[r];
   }
-  if (tid < 201 && brow < nu && bcol < nu) P[brow][bcol] = bv0 - sum4(bs);
+  EKF_STAMPW(34);  // (the wave's tile stored)
+  *(tid < 201 && brow < nu && bcol < nu ? &P[brow][bcol] : &sh.junk[wv][L.ln]) = bv0 - sum4(bs);
 }
 
 // P = D − K'·M'full with M'full = [M' (rows 0..31); K'[:, 0..32)ᵀ (rows 32..63: a Joseph chunk
@@ -1020,7 +1051,8 @@ __device__ __forceinline__ void rebuild_p_simple(ChainSharedT<false>& sh, const 
 // once) × the three column tiles, interleaved. Rows / columns ≥ kMaxU are clamped on read and never
 // stored; a wave reads and writes only its own rows.
 __device__ __forceinline__ void rebuild_p_joseph(ChainSharedT<true>& sh, const ChainLane& L,
-                                                 int nu) {
+                                                 int nu, unsigned seq) {
+  (void)seq;  // (diagnostic stamps)
   auto& P = sh.im.D;
   const int wv = L.wv, i16 = L.i16, k4 = L.k4;
   if (wv < 3) {
@@ -1057,10 +1089,14 @@ __device__ __forceinline__ void rebuild_p_joseph(ChainSharedT<true>& sh, const C
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 16 * wv + k4 + 4 * r;
-        if (row < nu && col < nu) P[row][col] = acc[tj][r];
+        *(row < nu && col < nu ? &P[row][col] : &sh.junk[wv][L.ln]) = acc[tj][r];
       }
     }
   }
+  else {  // wave 3 has no tile: x_in[U]
+    store_x_in(sh, L.ln, nu, prev_x_at_U(sh, L.ln));
+  }
+  EKF_STAMPW(34);  // (the wave's tiles stored)
 }
 
 // The predicted pose (slam.cpp:184-196) of a rebuilding chunk, from x' of the pose: one lane of
@@ -1082,7 +1118,8 @@ __device__ __forceinline__ void pick_predicted_pose(ChainSharedT<J>& sh, const M
   }
 }
 
-// The rebuild's phases in order: operands, the previous predict, K' / M', P, the predicted pose.
+// The rebuild's phases in order: operands, the previous predict (and the map of U into U'), K' / M',
+// P, the predicted pose.
 template <typename T, bool J>
 __device__ __forceinline__ void rebuild_block(ChainSharedT<J>& sh, const MsgDesc& d,
                                               ChainLoads<T, J>& loads, const T* Sp, const double* xp,
@@ -1094,22 +1131,30 @@ __device__ __forceinline__ void rebuild_block(ChainSharedT<J>& sh, const MsgDesc
   land_rebuild_operands(sh, loads, Sp, xp, ld, rp, ctl, L.tid, nu, np, early);
   __syncthreads();
   EKF_STAMP(21);
-  predict_prev(sh, L.tid, nu, np, q);
+  // (wave 3's threads have no special entry: the map instead, not before)
+  if (L.wv == 3)
+    map_U_into_prev(sh, L.ln, nu);
+  else
+    predict_prev(sh, L.tid, nu, np, q);
   __syncthreads();
 
   EKF_STAMP(3);
   EKF_STAMP(4);
   if constexpr (!J)
-    L.wv == 3 ? rebuild_km_simple<true>(sh, L, nu, np) : rebuild_km_simple<false>(sh, L, nu, np);
+    L.wv == 3 ? rebuild_km_simple<true>(sh, L, nu, np, seq)
+              : rebuild_km_simple<false>(sh, L, nu, np, seq);
   else
-    L.wv == 3 ? rebuild_km_joseph<true>(sh, L, nu, np) : rebuild_km_joseph<false>(sh, L, nu, np);
+    L.wv == 3 ? rebuild_km_joseph<true>(sh, L, nu, np, seq)
+              : rebuild_km_joseph<false>(sh, L, nu, np, seq);
   EKF_STAMP(7);
+  EKF_STAMPW(22);  // (each wave's end of the K' / M' phase)
   __syncthreads();
   EKF_STAMP(5);
   if constexpr (!J)
-    rebuild_p_simple(sh, L, nu);
+    rebuild_p_simple(sh, L, nu, seq);
   else
-    rebuild_p_joseph(sh, L, nu);
+    rebuild_p_joseph(sh, L, nu, seq);
+  EKF_STAMPW(26);  // (each wave's end of the P phase)
   EKF_STAMPT(10, 64);
   EKF_STAMPT(11, 128);
   EKF_STAMPT(13, 192);
@@ -1117,7 +1162,7 @@ __device__ __forceinline__ void rebuild_block(ChainSharedT<J>& sh, const MsgDesc
     pick_predicted_pose(sh, d, ci);
     EKF_STAMPT(8, 128);
   }
-  EKF_STAMPT(9, 192);  // (x_in[U]: wave 3 in the K' / M' phase)
+  EKF_STAMPT(9, 192);  // (wave 3's end; its x_in[U]: K' / M' phase, Joseph form P phase)
 }
 
 // ---- A1, gathering: Σ_in[U, U], x[U] and the predicted pose from this chunk's own Σ_in / x ---------

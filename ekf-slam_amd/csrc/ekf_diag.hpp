@@ -22,6 +22,12 @@
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)                   \
       g_stamps[512 * (seq & 3) + (i)] = (v);                                      \
   } while (0)
+// one stamp per wave, by its lane 0: slot i + the wave's index
+#define EKF_STAMPW(i)                                                             \
+  do {                                                                            \
+    if (blockIdx.x == 0 && blockIdx.y == 0 && (threadIdx.x & 63) == 0)            \
+      g_stamps[512 * (seq & 3) + (i) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memtime(); \
+  } while (0)
 // tools/diag_blocks.py: filter 0's chain block Σ[U, U] and x[U] as the corrections start (predict
 // folded in), per chunk sequence number mod 64.
 #define EKF_DUMP_BLOCK(seq)                                                         \
@@ -54,6 +60,9 @@
   } while (0)
 #define EKF_STAMPV(i, v) \
   do {                   \
+  } while (0)
+#define EKF_STAMPW(i) \
+  do {                \
   } while (0)
 #define EKF_DUMP_BLOCK(seq) \
   do {                      \

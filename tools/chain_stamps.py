@@ -72,6 +72,12 @@ print(f"N={N} {DT}, chunk {-1 - int(os.environ.get('WHICH', '1'))} of {T} messag
       f"the chunk's stamp 0); chunk starts of the ring, relative: {sorted(ring[:, 0] - ring[:, 0].min())}")
 for k in (14, 1, 21, 15, 17, 3, 7, 5, 10, 11, 13, 8, 9, 6, 2, 18, 19, 12, 16, 40):
     print(f"{names[k]:24s} {s[k] - t0:8d}")
+# per-wave stamps (EKF_STAMPW: slot + wave) of the rebuild's two MFMA phases, from the phase's start
+# (stamp 3: the barrier behind the previous predict; stamp 5: the barrier behind K' / M')
+for base, name, ref in ((30, "K'/M' tiles stored", 3), (22, "K'/M' phase end", 3),
+                        (34, "P tile(s) stored", 5), (26, "P phase end", 5)):
+    print(f"{name:32s} waves 0-3 from chunk start {[int(s[base + v] - t0) for v in range(4)]}"
+          f"  from the phase's barrier {[int(s[base + v] - s[ref]) for v in range(4)]}")
 m = int(sc.count[w + T - 1 - int(os.environ.get("WHICH", "1"))])
 steps = [int(s[64 + 8 * c] - t0) for c in range(m)]
 print("step starts:", steps)
