@@ -691,6 +691,82 @@ int ekf_set_state(ekf_t h, int f, const double* state, const double* sigma, cons
   return EKF_OK;
 }
 
+// ekf_get_state + ekf_get_map_odom on `src`, ekf_set_state + ekf_set_odom on `dst`, without the
+// host in between (k_copy_state, ekf_copy.hip): the same element rules as the two above, and the
+// planner's t_odom_robot and pending predict carried as well.
+int ekf_copy_state(ekf_t dst, int fd, ekf_t src, int fs) {
+  if (!dst || !src || fd >= dst->F || fs >= src->F || (fd >= 0 && fs < 0)) return EKF_E_ARG;
+  if (fd < 0 && fs < 0 && dst->F != src->F) return EKF_E_ARG;
+  if (dst->cfg.n_landmarks < src->cfg.n_landmarks || dst->cfg.device != src->cfg.device)
+    return EKF_E_ARG;
+  if (int rc = settle(src)) return rc;
+  if (dst != src)
+    if (int rc = settle(dst)) return rc;
+  // a filter onto itself is left out: nothing of it is read, written or forgotten
+  const int skip = dst == src ? fs : -1;
+  if (dst == src && (fs < 0 || fd == fs)) return EKF_OK;
+  hipSetDevice(dst->cfg.device);
+  const int f0 = fd < 0 ? 0 : fd, nf = fd < 0 ? dst->F : 1;
+  int *spar = nullptr, *dpar = nullptr;
+  auto carve = [&](char* base) {
+    Carver c{base};
+    spar = c.take<int>(src->F);
+    dpar = c.take<int>(dst->F);
+    return c.off;
+  };
+  if (int rc = dst->eval_buf.reserve(carve(nullptr))) return rc;
+  carve(dst->eval_buf.get());
+  std::vector<int> par(std::max(src->F, dst->F));
+  for (int f = 0; f < src->F; ++f) par[f] = src->plan.parity(f);
+  HIPCHK(hipMemcpy(spar, par.data(), src->F * sizeof(int), hipMemcpyHostToDevice));
+  for (int f = 0; f < dst->F; ++f) par[f] = dst->plan.parity(f);
+  HIPCHK(hipMemcpy(dpar, par.data(), dst->F * sizeof(int), hipMemcpyHostToDevice));
+  CopyArgs a{};
+  for (int p = 0; p < 2; ++p) {
+    a.src_sig[p] = src->sig[p].get();
+    a.src_x[p] = src->x[p].get();
+    a.dst_sig[p] = dst->sig[p].get();
+    a.dst_x[p] = dst->x[p].get();
+  }
+  a.src_sig_stride = src->sig_stride;
+  a.src_x_stride = src->x_stride;
+  a.src_ctl = src->ctl.get();
+  a.src_par = spar;
+  a.n_src = src->n;
+  a.ld_src = src->ld;
+  a.dst_sig_stride = dst->sig_stride;
+  a.dst_x_stride = dst->x_stride;
+  a.dst_ctl = dst->ctl.get();
+  a.dst_par = dpar;
+  a.n_dst = dst->n;
+  a.ld_dst = dst->ld;
+  a.src_f = fs;
+  a.skip = skip;
+  a.prior = dst->cfg.init_var;
+  // fp64 pipeline destinations keep Σ exactly symmetric (ekf_set_state's rule)
+  const bool sym = dst->w == 8 && !dst->resident;
+  // A fork splits its destination filters over enough workgroups to fill the device (a few per
+  // CU), each reading its source tile once; the other forms have one workgroup per tile and filter.
+  const int tiles = ((dst->ld + kCopyTile - 1) / kCopyTile) * ((dst->n + kCopyTile - 1) / kCopyTile);
+  const int blocks = std::min(nf, (2048 + tiles - 1) / tiles);
+  a.fpb = fs >= 0 ? (nf + blocks - 1) / blocks : 1;
+  const int per_launch = 65535;  // (the grid's z limit, in workgroups of fpb filters)
+  for (int k = 0; k < nf; k += per_launch * a.fpb) {
+    a.dst_f0 = f0 + k;
+    a.nf = std::min(nf - k, per_launch * a.fpb);
+    HIPCHK(launch_copy_state(a, src->w == 4, dst->w == 4, sym, dst->stream.get()));
+  }
+  for (int k = f0; k < f0 + nf; ++k) {
+    if (k == skip) continue;
+    const int from = fs >= 0 ? fs : k;
+    const std::array<double, 3> odom = src->plan.odom(from);
+    dst->plan.forget(k);
+    dst->plan.set_pending(k, src->plan.pending(from));
+    dst->plan.set_odom(k, odom[0], odom[1], odom[2]);
+  }
+  return drain(dst);
+}
+
 int ekf_get_status(ekf_t h, int f, unsigned* flags) {
   if (!valid(h, f) || !flags) return EKF_E_ARG;
   if (int rc = settle(h)) return rc;

@@ -1,5 +1,6 @@
 // Kernel launchers (each defined beside its kernel: ekf_chain.hip, ekf_factors.hip,
-// ekf_sigma_pass.hip, ekf_assoc.hip, ekf_resident.hip, plan_kernels.hip, ekf_small.hip; called by
+// ekf_sigma_pass.hip, ekf_assoc.hip, ekf_resident.hip, plan_kernels.hip, ekf_small.hip,
+// ekf_copy.hip; called by
 // the host scheduler in ekf_sched.cpp).
 // Optional e0/e1: timing events carried by the dispatch itself (kernel execution time).
 #pragma once
@@ -252,6 +253,38 @@ template <typename T>
 hipError_t launch_eval_match(const EvalArgs& a, const EvalTruth& t, double gate2, const MatchOut& o,
                              int n_filters, hipStream_t s, hipEvent_t e0 = nullptr,
                              hipEvent_t e1 = nullptr);
+
+// ekf_copy_state (ekf_copy.hip): Σ, x, t_map_odom and the counter of source filters into nf
+// destination filters dst_f0 + k, each side's current "in" copy, on 64 × 64 tiles of the
+// destination Σ (columns up to ld_dst included: the padding is written as zero). The handles may be
+// one and the same; nothing of the source is written.
+constexpr int kCopyTile = 64;
+struct CopyArgs {
+  const void* src_sig[2];  // Σ ping-pong copies, filter 0 (fp64 or fp32: src_f32)
+  size_t src_sig_stride;   // elements between filters
+  const double* src_x[2];
+  size_t src_x_stride;
+  const FilterCtl* src_ctl;
+  const int* src_par;      // [F_src]: the copy each source filter's next chunk would read
+  int n_src, ld_src;
+  void* dst_sig[2];
+  size_t dst_sig_stride;
+  double* dst_x[2];
+  size_t dst_x_stride;
+  FilterCtl* dst_ctl;
+  const int* dst_par;      // [F_dst]
+  int n_dst, ld_dst;       // n_dst >= n_src: rows and columns beyond n_src get the prior's Σ₀
+  int src_f;               // >= 0: every destination filter receives this one; < 0: each receives
+                           // the source filter of its own index (fpb = 1)
+  int dst_f0, nf;
+  int fpb;                 // destination filters per workgroup, which reads its source tile once
+  int skip;                // this destination filter is the source itself and is left out (−1: none)
+  double prior;            // the destination's init_var
+};
+// sym: the destination is an fp64 pipeline handle, whose Σ takes the element on or above the
+// diagonal and its mirror below (not with dst_f32).
+hipError_t launch_copy_state(const CopyArgs& a, bool src_f32, bool dst_f32, bool sym,
+                             hipStream_t s);
 
 // Σ₀ diagonal: Σ[i][i] = v for i ≥ 3 (the rest is zero-filled by the caller).
 template <typename T>

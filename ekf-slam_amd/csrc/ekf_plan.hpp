@@ -77,6 +77,7 @@ class Planner {
   bool joseph() const { return joseph_; }
   int parity(int f) const { return parity_[f]; }
   bool pending(int f) const { return pending_[f] != 0; }
+  const std::array<double, 3>& odom(int f) const { return odom_[f]; }  // t_odom_robot (θ, x, y)
   int prev_m(int f) const { return prev_m_[f]; }
   const std::array<int, kMaxChunk>& prev_ids(int f) const { return prev_ids_[f]; }
 

@@ -559,6 +559,61 @@ int ekf_sim_run_lidar(ekf_sim_t s, lm_t lm, int T, const double* wheel_cmd,
   return run_lidar(s, lm, T, wheel_cmd, cfg);
 }
 
+// Every filter of dst continues src_filter's run: the filter by ekf_copy_state's fork form, the
+// simulator's own per-filter state by device copies behind it, the counters on the host.
+int ekf_sim_fork(ekf_sim_t dst, ekf_sim_t src, int src_filter) {
+  if (!dst || !src || src_filter < 0 || src_filter >= src->info.F) return EKF_E_ARG;
+  const ekf_sim_config &d = dst->cfg, &c = src->cfg;
+  if (dst->L != src->L || d.ticks_per_msg != c.ticks_per_msg || d.wheel_radius != c.wheel_radius ||
+      d.track_width != c.track_width || d.start_theta != c.start_theta ||
+      d.start_x != c.start_x || d.start_y != c.start_y)
+    return EKF_E_ARG;
+  // (checks everything before it touches anything, and waits for both handles' work)
+  if (int rc = ekf_copy_state(dst->h, -1, src->h, src_filter)) return rc;
+  hipSetDevice(dst->info.device);
+  // both simulators idle: nothing reads or writes the per-filter state copied below
+  if (hipStreamSynchronize(src->sst.get()) != hipSuccess ||
+      hipStreamSynchronize(dst->sst.get()) != hipSuccess)
+    return EKF_E_HIP;
+  const size_t F = static_cast<size_t>(dst->info.F), L = static_cast<size_t>(src->L);
+  const size_t words = (L + 31) / 32, fs = static_cast<size_t>(src_filter);
+  // the source filter's poses (hits = 0), sighted set and map, once for every destination filter
+  std::vector<SimState> st(F);
+  std::vector<unsigned> sighted(F * words);
+  std::vector<double> lm(F * L * 2);
+  if (hipMemcpy(st.data(), src->st.get() + fs, sizeof(SimState), hipMemcpyDeviceToHost) !=
+          hipSuccess ||
+      hipMemcpy(sighted.data(), src->sighted.get() + fs * words, words * sizeof(unsigned),
+                hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(lm.data(), src->lm.get() + fs * L * 2, L * 2 * sizeof(double),
+                hipMemcpyDeviceToHost) != hipSuccess)
+    return EKF_E_HIP;
+  st[0].hits = 0;
+  for (size_t f = 1; f < F; ++f) {
+    st[f] = st[0];
+    std::copy_n(sighted.begin(), words, sighted.begin() + f * words);
+    std::copy_n(lm.begin(), L * 2, lm.begin() + f * L * 2);
+  }
+  // filters [lo, hi) of dst; the source filter itself is left untouched
+  const auto upload = [&](size_t lo, size_t hi) {
+    const size_t k = hi - lo;
+    return k == 0 ||
+           (hipMemcpy(dst->st.get() + lo, st.data(), k * sizeof(SimState),
+                      hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(dst->sighted.get() + lo * words, sighted.data(),
+                      k * words * sizeof(unsigned), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(dst->lm.get() + lo * L * 2, lm.data(), k * L * 2 * sizeof(double),
+                      hipMemcpyHostToDevice) == hipSuccess);
+  };
+  if (dst == src ? !(upload(0, fs) && upload(fs + 1, F)) : !upload(0, F)) return EKF_E_HIP;
+  for (size_t f = 0; f < F; ++f)
+    if (dst != src || f != fs)
+      for (int k = 0; k < 3; ++k) dst->host_odom[3 * f + k] = st[0].odom[k];
+  dst->tick = src->tick;
+  dst->msg = src->msg;
+  return EKF_OK;
+}
+
 int ekf_sim_set_collisions(ekf_sim_t s, double collision_radius, double obstacle_radius) {
   if (!s || !(collision_radius >= 0.0) || !(obstacle_radius >= 0.0)) return EKF_E_ARG;
   s->hit_r = collision_radius > 0.0 ? collision_radius + obstacle_radius : 0.0;

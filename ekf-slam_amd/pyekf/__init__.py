@@ -53,6 +53,7 @@ EXPORTS = [
     "ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match",
     "ekf_sim_lidar_config_default", "ekf_sim_run_lidar", "lm_fetch_ranges",
     "ekf_sim_set_collisions", "ekf_sim_collisions", "ekf_sim_last_us",
+    "ekf_copy_state", "ekf_sim_fork",
 ]
 TRACE_EXPORTS = ("ekf_trace_enable", "ekf_trace_count", "ekf_trace_read", "ekf_trace_clear",
                  "slam_replay_trace")
@@ -62,9 +63,10 @@ MATCH_EXPORTS = ("ekf_eval_match", "ekf_sim_run_assoc", "ekf_sim_eval_match")
 LIDAR_EXPORTS = ("ekf_sim_lidar_config_default", "ekf_sim_run_lidar", "lm_fetch_ranges")
 COLLIDE_EXPORTS = ("ekf_sim_set_collisions", "ekf_sim_collisions")
 SIM_DEV_EXPORTS = ("ekf_sim_last_us",)  # measurement hook (EKF_SIM_TIMING), not part of the feature
+COPY_EXPORTS = ("ekf_copy_state", "ekf_sim_fork")
 LATER_EXPORTS = (TRACE_EXPORTS + ("ekf_replay_resident", "lm_replay_resident") + EVAL_EXPORTS +
                  MATCH_EXPORTS + ("ekf_chain_path_counts",) + LIDAR_EXPORTS + COLLIDE_EXPORTS +
-                 SIM_DEV_EXPORTS)
+                 SIM_DEV_EXPORTS + COPY_EXPORTS)
 EKF_MATCH_MAX_MAP = 1024
 EKF_EVAL_POSE_NOT_PD, EKF_EVAL_LM_NOT_PD = 1, 2
 SENSE_NEAREST, SENSE_SURVEY, SENSE_ALL = 0, 1, 2
@@ -258,6 +260,8 @@ def lib():
             "ekf_sim_set_collisions": (_i, [_vp, _d, _d]),
             "ekf_sim_collisions": (_i, [_vp, _vp, _vp]),
             "ekf_sim_last_us": (_i, [_vp, _dp]),
+            "ekf_copy_state": (_i, [_vp, _i, _vp, _i]),
+            "ekf_sim_fork": (_i, [_vp, _vp, _i]),
         }
         for name, (res, argt) in sig.items():
             # (EKF_LIB naming a library built from an earlier commit, for the A/B tools: it loads
@@ -503,6 +507,14 @@ class EKF:
         _check(lib().ekf_set_state(self.h, f, _ptr(state), _ptr(sigma), _ptr(tmo), counter),
                "ekf_set_state")
 
+    def copy_state_from(self, src, src_filter=None, dst_filter=None):
+        """ekf_copy_state: filter state from the handle ``src`` on the device, as state() on it
+        and set_state() + set_odom() here would leave it. src_filter and dst_filter given: one
+        filter onto one; src_filter alone: a fork, every filter here receives it; neither: a swarm
+        hand-over, filter f receives filter f."""
+        _check(lib().ekf_copy_state(self.h, -1 if dst_filter is None else dst_filter, src.h,
+                                    -1 if src_filter is None else src_filter), "ekf_copy_state")
+
     def defer(self, on=True):
         _check(lib().ekf_defer(self.h, int(on)), "ekf_defer")
 
@@ -741,6 +753,11 @@ class Sim:
         self.T = T
         if T > 0:
             det._ran_lidar(T * self.F, c.n_beams, c.max_markers)
+
+    def fork_from(self, src, src_filter):
+        """ekf_sim_fork: every filter of this simulator continues filter ``src_filter`` of the
+        simulator ``src`` (which may be this one) under its own seed."""
+        _check(lib().ekf_sim_fork(self.h, src.h, src_filter), "ekf_sim_fork")
 
     def set_collisions(self, collision_radius, obstacle_radius=0.038):
         """ekf_sim_set_collisions: from the next run on the true pose is pushed out of the map's

@@ -295,6 +295,39 @@ int ekf_set_state(ekf_t h, int filter, const double* state, const double* sigma,
                   const double* t_map_odom, unsigned counter);
 int ekf_get_status(ekf_t h, int filter, unsigned* flags); /* and clears them */
 
+/* ---- fork and hand over filter state on the device ---- */
+/* A filter's state from one handle into another without the host: what
+ *   ekf_get_state(src, fs, x, S, &cnt); ekf_get_map_odom(src, fs, tmo);
+ *   ekf_set_state(dst, fd, x', S', tmo, cnt); ekf_set_odom(dst, fd, src's t_odom_robot)
+ * leaves, bit for bit, by one copy-and-convert kernel over Σ (no n × ld Σ crosses PCIe, 2.1 MB per
+ * filter at N = 256, and any number of filters go in one call).
+ *   dst_filter >= 0, src_filter >= 0   one filter onto one filter;
+ *   dst_filter <  0, src_filter >= 0   a fork: every filter of dst receives src_filter's state;
+ *   both < 0                           a swarm hand-over: filter f receives filter f (equal
+ *                                      n_filters);
+ *   dst_filter >= 0, src_filter <  0   EKF_E_ARG.
+ * dst == src is allowed (a fork inside one swarm); a filter copied onto itself is skipped entirely.
+ * Any pairing of resident fp64, pipeline fp64 and pipeline fp32 handles on one device, with
+ * N_dst >= N_src. A larger destination is padded with the constructor's state (x', S'): state 0,
+ * dst's init_var on the new diagonal entries, 0 everywhere else.
+ * The rules of ekf_get_state / ekf_set_state hold: the source element is widened to double exactly;
+ * an fp64 destination stores it, an fp32 destination its static_cast<float>; an fp64 pipeline
+ * destination takes the element on or above the diagonal and mirrors it below (its Σ pass relies on
+ * exact symmetry, and resident and fp32 sources are symmetric only up to rounding), every other
+ * destination stores Σ as given; columns n..ld of every written row are written as zero. Both
+ * handles are settled first (what is planned runs, both streams drain, a device replay's planning
+ * state is adopted); the data is read from the source's and written to the destination's current
+ * copy, and the destination forgets what ekf_set_state makes it forget.
+ * Two things the host route cannot carry make the copy a clone, whose next message does what the
+ * source's next message would: src's host-side t_odom_robot (after a device replay or a simulator
+ * run, the run's last odometry pose) and src's pending predict (ekf_predict).
+ * The destination's status flags, decisions, pose trace, ekf_chain_path_counts counters and Joseph
+ * setting are left alone; the source is only read. Synchronises, like ekf_reset.
+ * EKF_E_ARG, detected before anything is touched: a NULL handle, a filter index out of range, the
+ * forbidden sign combination, unequal n_filters in the swarm form, N_dst < N_src, handles on
+ * different devices. */
+int ekf_copy_state(ekf_t dst, int dst_filter, ekf_t src, int src_filter);
+
 /* ---- the pose trace: every message's posterior, recorded on the device ---- */
 /* The per-message outputs of the reference node (the posterior pose and t_map_odom it publishes as
  * TF, green/odom and green/path after every MarkerArray, slam.cpp:273-291) without a

@@ -143,6 +143,22 @@ void ekf_sim_lidar_config_default(ekf_sim_lidar_config*);
 int ekf_sim_run_lidar(ekf_sim_t s, lm_t lm, int T, const double* wheel_cmd,
                       const ekf_sim_lidar_config* cfg);
 
+/* Monte-Carlo from a common prior: every filter of dst continues src_filter's run under its own
+ * seed (dst's seed + f0 + f), on the device.
+ *   The filters: ekf_copy_state(dst's handle, -1, src's handle, src_filter) (ekf.h), the handle's
+ *     t_odom_robot included.
+ *   The simulator: src_filter's true and odometry poses (with the collision count 0), its sighted
+ *     set and its map landmarks[src_filter][L][2] into every dst filter; dst's tick and message
+ *     counters become src's, so the draw indices go on from where the source's run stands.
+ * The two simulators must agree on L, ticks_per_msg, wheel_radius, track_width and the start pose
+ * (the map frame of ekf_sim_eval: a forked swarm scores in the source's frame); slip, sensor_sigma,
+ * max_range, max_markers, marker_stride, seed, f0 and the collision setting may differ.
+ * dst == src forks one filter over its own swarm; src_filter itself is left untouched.
+ * Synchronises. EKF_E_ARG, with nothing changed and no counter moved: a NULL simulator, src_filter
+ * out of range, a configuration mismatch, anything ekf_copy_state rejects (a smaller destination N,
+ * another device). */
+int ekf_sim_fork(ekf_sim_t dst, ekf_sim_t src, int src_filter);
+
 /* Collisions with the map's cylinders (nusim.cpp:232-254), for ekf_sim_run, ekf_sim_run_assoc and
  * ekf_sim_run_lidar alike. Once per tick, after FKin, with the true pose at (x, y, θ) the landmarks
  * are tested in id order, R = collision_radius + obstacle_radius:
