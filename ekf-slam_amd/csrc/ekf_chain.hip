@@ -157,14 +157,16 @@ __device__ __forceinline__ void lds_wait_ge(const int* flag, int v) {
 // allocation is not the one of the kernel's four wave programs together (the shared allocation
 // spilled SGPRs, and their reloads sat in this loop). LDS through address-space-3 references.
 //
-// Two programs from one body (wave0_steps): the generic one, chain_wave0, holds every case; the
-// lean one, chain_wave0_lean, holds the common case alone — a landmark already in the map, a valid
-// id, a finite nonsingular S, angles within normalize_angle_near's range — and neither the first
-// sighting's cos / sin, nor the generic normalize_angle, the re-done scalars, the skip's zeroing or
-// the status word: a third of the code, fewer blocks on the step's path and fewer registers to
-// save around the call. It never computes a rare case: it detects one and returns the index of
-// the first step it did not run, and the generic program resumes there (k_chain). Both evaluate
-// the one body's expressions in the one order, so a step has the same bits whichever ran it.
+// Two programs: the generic one, chain_wave0 (wave0_steps), holds every case; the lean one,
+// chain_wave0_lean (wave0_lean_steps), holds the common case alone — a landmark already in the
+// map, a valid id, a finite nonsingular S, angles within normalize_angle_near's range — and neither
+// the first sighting's cos / sin, nor the generic normalize_angle, the re-done scalars, the skip's
+// zeroing or the status word. It never computes a rare case: it detects one and returns the index
+// of the first step it did not run, and the generic program resumes there (k_chain). The lean
+// program's step spells the generic step's expressions in the generic step's order (every sum of
+// products an explicit fma), so a step has the same bits whichever ran it
+// (tests/test_gpu_chain_fastpath.py, tests/test_gpu_lean_straight.py); what differs is the control
+// flow around them: the lean step is straight-line code.
 template <bool J>
 using LdsChain = __attribute__((address_space(3))) ChainSharedT<J>;
 typedef __attribute__((address_space(3))) const MsgDesc LdsDesc;
@@ -187,11 +189,10 @@ __device__ __forceinline__ void lds_wait_ge3(const __attribute__((address_space(
 // c0: the step to start at. What step c0 > 0 would hold in registers had the function run from
 // step 0 is all in LDS: wave 0 stores its cross (the next step's pk / pm) and x[U] every step,
 // and wave 3 stores the rest of the block with the same operands in the same order, so the block
-// after step c0 − 1 is whole once pdone ≥ c0. LEAN: only c0 = 0. Returns the first step not run
-// (the generic program: m).
-template <bool J, bool LEAN>
-__device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, int m, int nu,
-                                           double r_noise, unsigned seq) {
+// after step c0 − 1 is whole once pdone ≥ c0.
+template <bool J>
+__device__ __forceinline__ void wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, int m, int nu,
+                                            double r_noise, unsigned seq) {
   constexpr int JM = ChainSharedT<J>::JM;
   const int lane = threadIdx.x & 63;
   (void)seq;  // (diagnostic stamps)
@@ -203,7 +204,7 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
   // them. Lanes ≥ |U| carry a clamped row and never store.
   const int lr = lane < kMaxU ? lane : kMaxU - 1;
   const int ul = sh.u[lr];
-  if (!LEAN && c0 > 0) {  // wave 3's step c0 − 1 outside the cross (the nx columns / rows below)
+  if (c0 > 0) {  // wave 3's step c0 − 1 outside the cross (the nx columns / rows below)
     lds_wait_ge3(&sh.pdone, c0);
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
   }
@@ -233,7 +234,6 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
   // the marker's measurement and skip flag, read one step ahead (the descriptor and the skip list
   // are constant during the chunk): their LDS round trip stays off the step's dependent chain
   const bool noinit = (d.flags & kNoInit) != 0;
-  if (LEAN && noinit) return 0;  // (an association chunk: the generic program's)
   double zn0 = 0.0, zn1 = 0.0;
   int skn = 0;
   if (c0 < m) {
@@ -241,36 +241,28 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
     zn1 = d.z[c0][1];
     skn = sh.skip[c0];
   }
-  // → whether marker c is the lean program's (LEAN; always true otherwise): a valid id and a
-  // landmark that is in the map. If not, nothing of its geometry is computed.
-  auto geometry = [&](int c) -> bool {
+  auto geometry = [&](int c) {
     const int pj = 3 + 2 * c;
     const double pose[3] = {readlane_f64(xl, 0), readlane_f64(xl, 1), readlane_f64(xl, 2)};
     lx = readlane_f64(xl, pj);
     ly = readlane_f64(xl, pj + 1);
-    if constexpr (LEAN) {
-      // a skipped marker or a first sighting (slam.cpp:213-216): wave-uniform, a scalar branch
-      if (__builtin_amdgcn_readfirstlane(skn || (lx == 0.0 && ly == 0.0))) return false;
-    } else {
-      init = false;
-      // slam.cpp:213-216 (zn, skn: marker c); a wave-uniform test, so a scalar branch
-      if (__builtin_amdgcn_readfirstlane(!skn && !noinit && lx == 0.0 && ly == 0.0)) {
-        init = true;
-        sh.any_init = 1;
-        lx = pose[1] + zn0 * cos(zn1 + pose[0]);
-        ly = pose[2] + zn0 * sin(zn1 + pose[0]);
-      }
+    init = false;
+    // slam.cpp:213-216 (zn, skn: marker c); a wave-uniform test, so a scalar branch
+    if (__builtin_amdgcn_readfirstlane(!skn && !noinit && lx == 0.0 && ly == 0.0)) {
+      init = true;
+      sh.any_init = 1;
+      lx = pose[1] + zn0 * cos(zn1 + pose[0]);
+      ly = pose[2] + zn0 * sin(zn1 + pose[0]);
     }
     range_bearing(pose, lx, ly, zhat, H0, H1, &braw, &bok);
-    return true;
   };
-  if (c0 < m && !geometry(c0)) return c0;
+  if (c0 < m) geometry(c0);
   for (int c = c0; c < m; ++c) {
     const int pj = 3 + 2 * c, nx = pj + 2;
     const bool more = c + 1 < m;
     EKF_STAMP(64 + 8 * c);
     const double z0 = zn0, z1 = zn1;
-    bool sk = !LEAN && skn != 0;  // (LEAN: geometry(c) let no skipped marker in)
+    bool sk = skn != 0;
     if (more) {  // marker c + 1's, for geometry(c + 1) and the next step
       zn0 = d.z[c + 1][0];
       zn1 = d.z[c + 1][1];
@@ -312,7 +304,6 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
       nv1 = normalize_angle_near(z1 - zhat[1], &nok);
       const bool good = !sk && bok && nok && inv2_ok(det, Si);
       if (!__builtin_amdgcn_readfirstlane(good)) {  // (uniform: every lane has the same scalars)
-        if constexpr (LEAN) return c;  // (nothing of step c is stored or published yet)
         if (!bok) zhat[1] = normalize_angle(braw);  // |θ| > π: the generic fmod path
         if (!sk && inv2(Sm, Si)) {
           nv0 = z0 - zhat[0];
@@ -400,7 +391,7 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
     const double V1 = J ? kb - fma(K0, Sm_keep[1], K1 * Sm_keep[3]) : 0.0;
     {
       double xt = xl;
-      if constexpr (!LEAN) xt = (init && ul == jx) ? lx : ((init && ul == jx + 1) ? ly : xt);
+      xt = (init && ul == jx) ? lx : ((init && ul == jx + 1) ? ly : xt);
       xt = xt + fma(K0, nv0, K1 * nv1);             // slam.cpp:261
       bool tok;                                     // slam.cpp:267 on lane 0, branch-free
       const double tn = normalize_angle_near(xt, &tok);
@@ -408,7 +399,6 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
       xt = lane == 0 ? tn : xt;
       // lane 0's θ beyond normalize_angle_near's range: the generic path (a scalar branch)
       if (__builtin_amdgcn_ballot_w64(!tok) & 1ull) {
-        if constexpr (LEAN) return c;  // (step c's first store is the one below)
         if (lane == 0) xt = normalize_angle(xraw);
       }
       xl = xt;
@@ -428,7 +418,7 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
         vd[0] = in ? V0 : 0.0;
         vd[1] = in ? V1 : 0.0;
         if (lane == 0)
-          for (int k = 0; k < 4; ++k) sh.Ss[cj][k] = !LEAN && sk ? 0.0 : Sm_keep[k];
+          for (int k = 0; k < 4; ++k) sh.Ss[cj][k] = sk ? 0.0 : Sm_keep[k];
       }
     }
     if (lane == 0) {
@@ -463,9 +453,7 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
           vx1[k] = sh.VU[cj][l][1];
         }
       }
-      // (LEAN, marker c + 1 not the lean program's: this step's cross update, which does not need
-      // that marker's geometry, then out)
-      const bool next_ok = geometry(c + 1);
+      geometry(c + 1);
       // wave 3's step c−1 writes outside this step's cross must land before this cross update
       // overwrites the nx columns / rows (waited for above already when c + 2 < m)
       if (c + 2 >= m && __builtin_amdgcn_readfirstlane(pd_early) < c) lds_wait_ge3(&sh.pdone, c);
@@ -496,25 +484,266 @@ __device__ __forceinline__ int wave0_steps(LdsChain<J>& sh, LdsDesc& d, int c0, 
       mp1 = mm1;
       vp0 = V0;
       vp1 = V1;
-      if (LEAN && !next_ok) return c + 1;
     }
     EKF_STAMP(70 + 8 * c);
   }
-  return m;
+}
+
+// The lean program: wave0_steps' step from c0 = 0 for common-case markers, as straight-line code.
+// → the first step it did not run (m: the whole chunk); nothing of that step is stored or
+// published, and every step before it is complete (its cross update included), so the generic
+// program resumes there from LDS.
+//
+// A step is two basic blocks, so that the scheduler can fill the f64 chains' latency (atan2, the
+// reciprocals) with the independent work beside them (the M row, ν, the cross update's FMAs and
+// stores, the publication):
+//   1. the step's scalars up to the new x — H·Σ products, S, S⁻¹, ν, the look-ahead operands, K;
+//   2. every store and the publication, geometry(c + 1) and the cross update.
+// Between them, the step's one test: a wave-uniform word that collects every rare case (marker c
+// skipped or sighted for the first time, found by geometry(c) a step earlier; a bearing, ν or θ
+// beyond normalize_angle_near's range; S singular or not finite) and whether wave 3 is behind
+// (pdone < c, the one place a spin can be needed; out of line). What it takes to get there:
+//   - the last step is peeled (More = false: no look-ahead, no cross update), so the loop's steps
+//     have a next marker without a test, and its look-ahead columns nx + 2 are read with a clamped
+//     index where the generic step tests c + 2 < m (unused when there is no marker c + 2);
+//   - lane 0's H, S⁻¹, ν (and S) go through a selected address like every other store here;
+//   - a rare marker's scalars are computed (on whatever its x holds) and discarded.
+template <bool J>
+__device__ __forceinline__ int wave0_lean_steps(LdsChain<J>& sh, LdsDesc& d, int m, int nu,
+                                                double r_noise, unsigned seq) {
+  constexpr int JM = ChainSharedT<J>::JM;
+  const int lane = threadIdx.x & 63;
+  (void)seq;  // (diagnostic stamps)
+  const int lr = lane < kMaxU ? lane : kMaxU - 1;
+  // Entry: every LDS read is issued before the first is needed; geometry(0) waits for x alone and
+  // the block reads land beside it. (An empty or an association chunk is the generic program's:
+  // the descriptor's flags are the first read back.)
+  const int flags = d.flags;
+  double xl = sh.xU[0][lr];
+  double zn0 = d.z[0][0], zn1 = d.z[0][1];
+  int skn = sh.skip[0];
+  double pk[5], pm[5], rn[2], qn[2];
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {  // pA of step 0 = {0, 1, 2, 3, 4}
+    pk[a] = sh.im.D[lr][a];
+    pm[a] = sh.im.D[a][lr];
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    rn[j] = sh.im.D[lr][5 + j];
+    qn[j] = sh.im.D[5 + j][lr];
+  }
+  if (m < 1 || (flags & kNoInit) != 0) return 0;
+  double kp0 = 0.0, kp1 = 0.0, mp0 = 0.0, mp1 = 0.0, vp0 = 0.0, vp1 = 0.0;
+  double H0[5], H1[5], zhat[2];
+  bool bok = true;
+  // marker c's ẑ and H from x after step c − 1 (zn, skn: marker c) → whether the marker is not the
+  // lean program's: skipped, or a first sighting (slam.cpp:213-216). Wave-uniform.
+  auto geometry = [&](int c) -> bool {
+    const int pj = 3 + 2 * c;
+    const double pose[3] = {readlane_f64(xl, 0), readlane_f64(xl, 1), readlane_f64(xl, 2)};
+    const double lx = readlane_f64(xl, pj), ly = readlane_f64(xl, pj + 1);
+    double braw;
+    range_bearing(pose, lx, ly, zhat, H0, H1, &braw, &bok);
+    return skn != 0 || (lx == 0.0 && ly == 0.0);
+  };
+  bool rare_next = geometry(0);
+  // step c; → true: not run (a rare case)
+  auto step = [&](int c, auto more_t) -> bool {
+    constexpr bool More = decltype(more_t)::value;  // a marker c + 1 follows
+    const int pj = 3 + 2 * c, nx = pj + 2;
+    EKF_STAMP(64 + 8 * c);
+    const double z0 = zn0, z1 = zn1;
+    bool rare = rare_next;
+    if constexpr (More) {  // marker c + 1's, for geometry(c + 1) and the next step
+      zn0 = d.z[c + 1][0];
+      zn1 = d.z[c + 1][1];
+      skn = sh.skip[c + 1];
+    }
+    double Si[4], Sm[4];
+    EKF_STAMP(65 + 8 * c);
+    const double dk1 = pk[1] - pk[3], dk2 = pk[2] - pk[4];
+    const double dm1 = pm[1] - pm[3], dm2 = pm[2] - pm[4];
+    const double ka = fma(H0[2], dk2, H0[1] * dk1), kb = fma(H1[2], dk2, fma(H1[1], dk1, -pk[0]));
+    const double mm0 = fma(H0[2], dm2, H0[1] * dm1), mm1 = fma(H1[2], dm2, fma(H1[1], dm1, -pm[0]));
+    {
+      double ta[5], tb[5];
+#pragma unroll
+      for (int a = 0; a < 5; ++a) {
+        const int l = a < 3 ? a : pj + a - 3;
+        ta[a] = readlane_f64(ka, l);
+        tb[a] = readlane_f64(kb, l);
+      }
+      const double ta1 = ta[1] - ta[3], ta2 = ta[2] - ta[4], tb1 = tb[1] - tb[3], tb2 = tb[2] - tb[4];
+      Sm[0] = fma(H0[2], ta2, H0[1] * ta1) + r_noise;
+      Sm[1] = fma(H0[2], tb2, H0[1] * tb1);
+      Sm[2] = fma(H1[2], ta2, fma(H1[1], ta1, -ta[0]));
+      Sm[3] = fma(H1[2], tb2, fma(H1[1], tb1, -tb[0])) + r_noise;
+    }
+    const double det = inv2_calc(Sm, Si);
+    const double nv0 = z0 - zhat[0];
+    bool nok;
+    const double nv1 = normalize_angle_near(z1 - zhat[1], &nok);
+    rare |= !(bok & nok & inv2_ok(det, Si));  // (&: no short-circuit branch)
+    // the next marker's cross operands after step c − 1 (wave0_steps)
+    double xr[5], xq[5];
+    int pd_early = 0;
+    if constexpr (More) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        xr[k] = pk[k];
+        xq[k] = pm[k];
+      }
+      pd_early = __hip_atomic_load(&sh.pdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const int cp = c > 0 ? c - 1 : 0;
+      const double mqx = sh.MU[cp][nx][0], mqy = sh.MU[cp][nx][1];
+      const double mq2x = sh.MU[cp][nx + 1][0], mq2y = sh.MU[cp][nx + 1][1];
+      const double kqx = sh.KU[cp][nx][0], kqy = sh.KU[cp][nx][1];
+      const double kq2x = sh.KU[cp][nx + 1][0], kq2y = sh.KU[cp][nx + 1][1];
+      xr[3] = rank2_sub(rn[0], kp0, kp1, mqx, mqy);
+      xr[4] = rank2_sub(rn[1], kp0, kp1, mq2x, mq2y);
+      xq[3] = rank2_sub(qn[0], kqx, kqy, mp0, mp1);
+      xq[4] = rank2_sub(qn[1], kq2x, kq2y, mp0, mp1);
+      if (J) {
+        const int cj = min(cp, JM - 1);
+        const double vqx = sh.VU[cj][nx][0], vqy = sh.VU[cj][nx][1];
+        const double vq2x = sh.VU[cj][nx + 1][0], vq2y = sh.VU[cj][nx + 1][1];
+        xr[3] = rank2_sub(xr[3], vp0, vp1, kqx, kqy);
+        xr[4] = rank2_sub(xr[4], vp0, vp1, kq2x, kq2y);
+        xq[3] = rank2_sub(xq[3], vqx, vqy, kp0, kp1);
+        xq[4] = rank2_sub(xq[4], vq2x, vq2y, kp0, kp1);
+      }
+    }
+    EKF_STAMP(66 + 8 * c);
+    const double K0 = fma(kb, Si[2], ka * Si[0]);
+    const double K1 = fma(kb, Si[3], ka * Si[1]);
+    const double V0 = J ? ka - fma(K0, Sm[0], K1 * Sm[2]) : 0.0;
+    const double V1 = J ? kb - fma(K0, Sm[1], K1 * Sm[3]) : 0.0;
+    double xt = xl + fma(K0, nv0, K1 * nv1);      // slam.cpp:261
+    bool tok;                                     // slam.cpp:267 on lane 0, branch-free
+    const double tn = normalize_angle_near(xt, &tok);
+    xt = lane == 0 ? tn : xt;
+    // The step's one test, before its first store. (Lane 0's word: the other lanes' differ in tok
+    // alone, which is about θ.)
+    const int out = static_cast<int>(__builtin_amdgcn_ballot_w64(rare | !tok) & 1ull);
+    const int behind = More ? __builtin_amdgcn_readfirstlane(pd_early) < c : 0;
+    if (__builtin_expect((out | behind) != 0, 0)) {
+      if (out) return true;
+      // wave 3's step c − 1 outside this step's cross must land before the reads of the cross
+      // after next and before this step's cross update overwrites the nx columns / rows
+      lds_wait_ge3(&sh.pdone, c);
+    }
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    EKF_STAMP(67 + 8 * c);
+    if constexpr (More) {  // the cross after next (nx + 2), before this step's cross update
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int col = min(nx + 2 + j, kMaxU - 1);
+        rn[j] = sh.im.D[lr][col];
+        qn[j] = sh.im.D[col][lr];
+      }
+    }
+    xl = xt;
+    ldsd* const sink = &sh.junk[0][lane];
+    // lane 0's records (up to 10 doubles from one selected base): the other lanes' go to the sink
+    // rows taken as one array, each lane's from its own 16 bytes on (lane 63 ends at entry 135 of
+    // 256; the tails lap over the neighbours' and the other waves' sinks, which nobody reads)
+    ldsd* const sink0 = &sh.junk[0][0] + 2 * lane;
+    *(lane < nu ? &sh.xU[0][lane] : sink) = xt;
+    {
+      const bool in = lane < nu, st = lane < kMaxU;
+      ldsd* kd = st ? &sh.KU[c][lane][0] : &sh.junk2[lane][0];
+      ldsd* md = st ? &sh.MU[c][lane][0] : &sh.junk2[lane][0];
+      kd[0] = in ? K0 : 0.0;
+      kd[1] = in ? K1 : 0.0;
+      md[0] = in ? mm0 : 0.0;
+      md[1] = in ? mm1 : 0.0;
+      if (J) {
+        const int cj = min(c, JM - 1);
+        ldsd* vd = st ? &sh.VU[cj][lane][0] : &sh.junk2[lane][0];
+        vd[0] = in ? V0 : 0.0;
+        vd[1] = in ? V1 : 0.0;
+        ldsd* sd = lane == 0 ? &sh.Ss[cj][0] : sink0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sd[k] = Sm[k];
+      }
+    }
+    ldsd* hd = lane == 0 ? &sh.Hs[c][0][0] : sink0;
+    ldsd* id = lane == 0 ? &sh.Sis[c][0] : sink0;
+    ldsd* nd = lane == 0 ? &sh.nu[c][0] : sink0;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+      hd[a] = H0[a];
+      hd[5 + a] = H1[a];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) id[k] = Si[k];
+    nd[0] = nv0;
+    nd[1] = nv1;
+    lds_publish3(&sh.pub, c + 1);
+    EKF_STAMP(68 + 8 * c);
+    if constexpr (More) {
+      // K and M of the five Bx rows / columns: broadcast LDS reads of what this step stored
+      double kx0[5], kx1[5], mx0[5], mx1[5], vx0[5], vx1[5];
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const int l = k < 3 ? k : nx + k - 3;
+        kx0[k] = sh.KU[c][l][0];
+        kx1[k] = sh.KU[c][l][1];
+        mx0[k] = sh.MU[c][l][0];
+        mx1[k] = sh.MU[c][l][1];
+        if (J) {
+          const int cj = min(c, JM - 1);
+          vx0[k] = sh.VU[cj][l][0];
+          vx1[k] = sh.VU[cj][l][1];
+        }
+      }
+      rare_next = geometry(c + 1);
+      // all rows × Bx columns: next step's pk
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const int col = k < 3 ? k : nx + k - 3;
+        pk[k] = rank2_sub(xr[k], K0, K1, mx0[k], mx1[k]);
+        if (J) pk[k] = rank2_sub(pk[k], V0, V1, kx0[k], kx1[k]);
+        *(lane < nu ? &sh.im.D[lane][col] : sink) = pk[k];
+      }
+      // Bx rows × every other column: next step's pm there
+      const bool later = lane >= 3 && lane < nu && lane != nx && lane != nx + 1;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) {
+        const int row = k < 3 ? k : nx + k - 3;
+        double v = rank2_sub(xq[k], kx0[k], kx1[k], mm0, mm1);
+        if (J) v = rank2_sub(v, vx0[k], vx1[k], K0, K1);
+        pm[k] = v;
+        *(later ? &sh.im.D[row][lane] : sink) = v;
+      }
+      kp0 = K0;
+      kp1 = K1;
+      mp0 = mm0;
+      mp1 = mm1;
+      vp0 = V0;
+      vp1 = V1;
+    }
+    EKF_STAMP(70 + 8 * c);
+    return false;
+  };
+  for (int c = 0; c + 1 < m; ++c)
+    if (step(c, std::true_type{})) return c;
+  return step(m - 1, std::false_type{}) ? m - 1 : m;
 }
 
 template <bool J>
 __device__ __noinline__ void chain_wave0(LdsChain<J>* shp, LdsDesc* dp, int c0, int m, int nu,
                                          double r_noise, unsigned seq) {
-  wave0_steps<J, false>(*shp, *dp, c0, m, nu, r_noise, seq);
+  wave0_steps<J>(*shp, *dp, c0, m, nu, r_noise, seq);
 }
 template <bool J>
 __device__ __noinline__ int chain_wave0_lean(LdsChain<J>* shp, LdsDesc* dp, int m, int nu,
                                              double r_noise, unsigned seq) {
   // (arguments arrive in vector registers: said to be wave-uniform here, the step loop's control
   // flow and addresses are scalar)
-  return wave0_steps<J, true>(*shp, *dp, 0, __builtin_amdgcn_readfirstlane(m),
-                              __builtin_amdgcn_readfirstlane(nu), readfirstlane_f64(r_noise), seq);
+  return wave0_lean_steps<J>(*shp, *dp, __builtin_amdgcn_readfirstlane(m),
+                             __builtin_amdgcn_readfirstlane(nu), readfirstlane_f64(r_noise), seq);
 }
 
 // The previous chunk's predict on the rebuild operands: v + α_i·Σ[0][j] +
@@ -1908,8 +2137,9 @@ __global__ __launch_bounds__(kChainThreads) void k_chain(PassArgs<T> A, int nchu
     // this chunk's own record (waves 1–2 write Z, Y through; then the pend patch and the rest)
     ChunkRec* const rec = A.rec + static_cast<size_t>(d.parity) * A.rec_stride + f;
     if (L.wv == 0) {
-      // A.chain_fast (EKF_CHAIN_FAST=1): the lean program as far as the chunk's markers are common
-      // cases, the generic one from the first that is not; otherwise the generic one from step 0
+      // A.chain_fast (the default): the lean program as far as the chunk's markers are common
+      // cases, the generic one from the first that is not; EKF_CHAIN_FAST=0: the generic one from
+      // step 0
       int c = 0;
       if (A.chain_fast) c = chain_wave0_lean<J>((LdsChain<J>*)(&sh), (LdsDesc*)(&d), m, nu, A.r, seq);
       if (c < m) chain_wave0<J>((LdsChain<J>*)(&sh), (LdsDesc*)(&d), c, m, nu, A.r, seq);

@@ -76,9 +76,10 @@ struct ekf_ctx {
   bool defer = false;            // ekf_defer: plan now, upload and launch later
   bool assoc_msg = true;         // unknown association by chunks (k_assoc_msg); EKF_ASSOC_MSG=0:
                                  // one association kernel + launch pair per marker
-  bool chain_fast = false;       // EKF_CHAIN_FAST=1: k_chain's lean wave-0 program runs the
-                                 // common-case corrections (off by default: DESIGN.md §5, round
-                                 // 12; bit-identical either way, tests compare the two)
+  bool chain_fast = true;        // k_chain's lean wave-0 program runs the common-case
+                                 // corrections; EKF_CHAIN_FAST=0: the generic program from step 0
+                                 // (rounds 12 and 16; bit-identical either way,
+                                 // tests compare the two)
   bool main_dirty = false;       // work on the main stream since the bulk stream last joined it
   bool main_unordered = false;   // the main stream ran descriptor-reading work (k_posterior) that
                                  // nothing on the bulk stream is ordered after: a device planner

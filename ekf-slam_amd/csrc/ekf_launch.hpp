@@ -43,7 +43,7 @@ struct PassArgs {
   int gather;           // chain (dev A/B, EKF_SERIAL_GATHER=1): in stream order every chunk
                         // gathers its complete Σ_in instead of a kLook rebuild
   int chain_fast;       // chain: wave 0 runs common-case corrections in its lean program
-                        // (EKF_CHAIN_FAST=1; by default every step in the generic one)
+                        // (the default; EKF_CHAIN_FAST=0: every step in the generic one)
   const MsgDesc* desc;
   int desc_stride;      // descriptors between consecutive chunks of a chain launch
   int n, ld, N, f0;

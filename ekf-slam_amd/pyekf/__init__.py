@@ -531,8 +531,8 @@ class EKF:
 
     def chain_path_counts(self, f=0):
         """(lean, generic): corrections the chain kernel's sequential wave has run for filter f in
-        its common-case program (EKF_CHAIN_FAST=1) and in its generic one since the handle's
-        creation or last reset (by default all of them in the generic one)."""
+        its common-case program and in its generic one since the handle's creation or last reset
+        (EKF_CHAIN_FAST=0: all of them in the generic one)."""
         a, b = C.c_ulonglong(0), C.c_ulonglong(0)
         _check(lib().ekf_chain_path_counts(self.h, f, C.byref(a), C.byref(b)),
                "ekf_chain_path_counts")

@@ -501,9 +501,9 @@ double ekf_sigma_pass_bytes(ekf_t h, int filters_in_launch);
  * wave that ran them: `lean` holds the common case alone (a mapped landmark, a valid id, a
  * nonsingular S, angles near (-π, π]) and hands a chunk over at the first marker that is anything
  * else; `generic` holds every case. Their sum is the corrections the kernel was given, skipped
- * ones included. The lean program is opt-in (EKF_CHAIN_FAST=1, read at ekf_create); by default
- * every correction runs in the generic program. Bit-identical either way. Synchronises. EKF_E_ARG: NULL arguments or a
- * filter out of range. */
+ * ones included. The lean program is on by default; EKF_CHAIN_FAST=0 (read at ekf_create) runs
+ * every correction in the generic program. Bit-identical either way. Synchronises. EKF_E_ARG:
+ * NULL arguments or a filter out of range. */
 int ekf_chain_path_counts(ekf_t h, int filter, unsigned long long* lean,
                           unsigned long long* generic);
 

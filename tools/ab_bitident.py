@@ -27,11 +27,17 @@ def child(tag):
     import pyekf
     from pyekf import synth
     res = {}
+    # EKF_CHAIN_FAST set by the caller: every leg's setting unless the leg sets its own (unset: each
+    # library's default, which differs between builds from before and after the lean program
+    # became the default)
+    fast = os.environ.get("EKF_CHAIN_FAST")
 
     def env(**kv):
         for k in ("EKF_SERIAL", "EKF_DEVSYNC", "EKF_STAGE", "EKF_CU_SPLIT", "EKF_RESIDENT",
                   "EKF_AM_XCD", "EKF_ASSOC_MSG", "EKF_CHAIN_FAST"):
             os.environ.pop(k, None)
+        if fast is not None:
+            os.environ["EKF_CHAIN_FAST"] = fast
         os.environ.update(kv)
 
     def keep(name, e, F=1):
